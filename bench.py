@@ -20,7 +20,11 @@ Per rank: random-init Mistral-7B weights in the exact Q4_K_M per-tensor layout (
 no real checkpoint), a synthetic prompt prefilled into the KV cache, W untimed warmup decode
 steps, then exactly K timed decode steps, each the full forward (embed, 32 blocks, lm_head,
 on-device greedy sampling) replayed from a captured hipGraph with the sampled token fed back on
-device.  Baseline: the reference's GPU target "<100 ms for a 50-token Mistral-7B response"
+device.  A plain run measures this headline only; `--full` adds every secondary measurement
+(TinyLlama, the other activation precision, the strategic-tier TP, collectives, goal->plan, the
+gRPC and co-resident tiers).  `--dump-outputs DIR` writes what the last timed step computed
+(DIR/tokens.npy: the sampled token of every timed step, DIR/logits.npy: the last step's logits).
+Baseline: the reference's GPU target "<100 ms for a 50-token Mistral-7B response"
 (docs/phases/04-AI-RUNTIME.md:334) => 500 tok/s.
 """
 from __future__ import annotations
@@ -49,8 +53,14 @@ def parse():
     ap.add_argument("--recipe", default="Q4_K_M")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--kv-dtype", default="bf16", help="KV cache dtype: bf16 (default) or fp8_e4m3")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the headline's outputs as DIR/<name>.npy (float32): tokens "
+                         "[batch, steps] = the token sampled in every timed step, logits [batch, vocab] = the last "
+                         "step's logits")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary measurements (TinyLlama, fp32-activation Mistral)")
+                    help="with --full: skip the secondary measurements (TinyLlama, fp32-activation Mistral)")
     ap.add_argument("--fp32-act", action="store_true",
                     help="headline with fp32 activations in the GEMVs instead of int8 (q8_1-style) ones")
     ap.add_argument("--no-tp", action="store_true", help="skip the strategic-tier TP secondary")
@@ -82,7 +92,10 @@ def spawn(args) -> int:
 
 
 def measure(preset: str, recipe: str, batch: int, prompt: int, steps: int, warmup: int, use_graph: bool, dist,
-            device: int, act_q8: bool = True, kv_dtype: str = "bf16"):
+            device: int, act_q8: bool = True, kv_dtype: str = "bf16", outputs: dict | None = None):
+    """Seconds of the `steps` timed decode steps and the engine's memory figures.  outputs: a dict
+    that receives what the timed path computed, as float32 arrays (tokens [batch, steps], the last
+    step's logits [batch, vocab])."""
     import torch
 
     from aios_amd.models.config import get_preset
@@ -112,10 +125,32 @@ def measure(preset: str, recipe: str, batch: int, prompt: int, steps: int, warmu
     dt = time.perf_counter() - t0
     hist = eng.decode_loop_history(batch, prompt + warmup + 1, steps)
     assert all(0 <= t < cfg.vocab_size for t in hist), "invalid token ids from decode loop"
+    if outputs is not None:
+        import numpy as np
+
+        outputs["tokens"] = np.asarray(hist, dtype=np.float32).reshape(batch, steps)  # (ids < 2^24: exact)
+        outputs["logits"] = np.asarray(eng.last_logits(batch), dtype=np.float32).reshape(batch, cfg.vocab_size)
     info = dict(weight_gb=round(eng.weight_bytes / 1e9, 3), kv_gb=round(eng.kv_bytes / 1e9, 3),
                 workspace_gb=round(eng.workspace_bytes / 1e9, 3))
     del eng
     return dt, info
+
+
+DUMP_BUDGET = 64 << 20  # bytes, all dumped arrays together
+
+
+def dump_outputs(directory: str, outputs: dict) -> None:
+    """DIR/<name>.npy per array; an array past its share of DUMP_BUDGET is written as a fixed
+    (seed 0) sample of its elements, in index order."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(outputs)) - 1024  # (.npy header)
+    for name, a in outputs.items():
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def measure_goal_plan(goals: int = 16, timeout_s: float = 90.0):
@@ -276,10 +311,14 @@ def main():
         dist = td
 
     act_q8 = not args.fp32_act
+    outputs = {} if args.dump_outputs and rank == 0 else None
     dt, info = measure(args.model, args.recipe, args.batch, args.prompt, args.steps, args.warmup,
-                       not args.no_graph, dist, device, act_q8, args.kv_dtype)
+                       not args.no_graph, dist, device, act_q8, args.kv_dtype, outputs)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
+    secondaries = args.full and not args.no_secondary  # (a plain run: the headline only)
     secondary = other_act = tp_dt = tp_info = None
-    if not args.no_secondary:
+    if secondaries:
         secondary, _ = measure("tinyllama-1.1b", "Q4_K_M", 1, args.prompt, args.steps, args.warmup,
                                not args.no_graph, dist, device)
         # the same Mistral decode with the other GEMV activation precision
@@ -297,7 +336,7 @@ def main():
                 print(f"[rank {rank}] tp_strategic failed: {tp_info['error']}", file=sys.stderr, flush=True)
 
     collectives = None
-    if world > 1 and not share and not args.no_secondary and not args.no_tp:
+    if world > 1 and not share and secondaries and not args.no_tp:
         try:
             collectives = measure_collectives(rank, world, device, gloo)
         except Exception as e:  # noqa: BLE001
@@ -305,7 +344,7 @@ def main():
             print(f"[rank {rank}] collectives failed: {collectives['error']}", file=sys.stderr, flush=True)
 
     goal_plan = None
-    if not args.no_secondary and not args.no_goal_plan and rank == 0:
+    if secondaries and not args.no_goal_plan and rank == 0:
         try:
             goal_plan = measure_goal_plan()
         except Exception as e:  # noqa: BLE001  (reported, never costs the headline)
@@ -314,7 +353,7 @@ def main():
 
     # BASELINE configs 2 and 4 (rank 0; each bounded, a failure is reported, never costs the headline)
     grpc_res = coresident = None
-    if not args.no_secondary and not args.no_serving and rank == 0:
+    if secondaries and not args.no_serving and rank == 0:
         try:
             edt, _ = measure("tinyllama-1.1b", "BF16", 1, args.prompt, 256, 16, not args.no_graph, None, device)
             grpc_res = measure_grpc()

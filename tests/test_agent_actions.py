@@ -6,6 +6,8 @@ import asyncio
 import http.server
 import json
 import os
+import pathlib
+import shutil
 import threading
 
 import pytest
@@ -148,15 +150,28 @@ def test_learning_agent(tmp_path):
     _agents(tmp_path, body)
 
 
-def test_creator_agent(tmp_path):
+@pytest.fixture
+def work_dir():
+    """A scratch directory whose whole path is fixed here.  The agents' keyword dispatch reads a
+    task's inputs as well as its description, and the tools take absolute paths only, so a path under
+    pytest's base temp (wherever the host puts it: below a directory named "...repo...", say) could
+    pick another action than the description asks for."""
+    d = pathlib.Path("/tmp") / f"aios-creator-{os.getpid()}"
+    shutil.rmtree(d, ignore_errors=True)
+    d.mkdir()
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
+def test_creator_agent(tmp_path, work_dir):
     async def body(mk, do):
         a = mk("creator")
-        sc = await do(a, "scaffold new project", name="p1", path=str(tmp_path / "proj"))
+        sc = await do(a, "scaffold new project", name="p1", path=str(work_dir / "proj"))
         assert sc["success"] and os.path.isdir(sc["output"]["path"])
-        g = await do(a, "generate code for an add function", file_path=str(tmp_path / "gen" / "add.py"))
+        g = await do(a, "generate code for an add function", file_path=str(work_dir / "gen" / "add.py"))
         assert g["success"], g
-        compile((tmp_path / "gen" / "add.py").read_text(), "add.py", "exec")
-        r = await do(a, "init repo", path=str(tmp_path / "repo"))
+        compile((work_dir / "gen" / "add.py").read_text(), "add.py", "exec")
+        r = await do(a, "init repo", path=str(work_dir / "repo"))
         assert r["success"] and len(r["commit"]) == 40, r
     _agents(tmp_path, body)
 

@@ -66,6 +66,31 @@ def test_gpus_8_one_device_per_rank():
     assert sorted(d["device"] for d in lines) == list(range(8))
 
 
+def test_dump_outputs_float32_npy_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per array; an array past its share of the byte budget is
+    written as the same seeded sample of its elements every time (two builds compare output for
+    output)"""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    toks = np.arange(24, dtype=np.float32).reshape(2, 12)
+    logits = np.random.default_rng(1).standard_normal((2, 5000)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"tokens": toks, "logits": logits})
+    assert sorted(os.listdir(tmp_path / "a")) == ["logits.npy", "tokens.npy"]
+    assert np.array_equal(np.load(tmp_path / "a" / "logits.npy"), logits)
+    assert np.load(tmp_path / "a" / "tokens.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 16384)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"tokens": toks, "logits": logits})
+    b, c = np.load(tmp_path / "b" / "logits.npy"), np.load(tmp_path / "c" / "logits.npy")
+    assert np.array_equal(b, c) and b.dtype == np.float32 and 1000 < b.size < logits.size
+    assert np.isin(b, logits).all()
+    assert np.array_equal(np.load(tmp_path / "b" / "tokens.npy"), toks)  # within its share: whole
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 16384
+
+
 def test_ranks_per_gpu_from_device_identity():
     """sharing is counted from the physical device identity, not device_count() (each
     rank may see only its own GPU)"""

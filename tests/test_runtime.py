@@ -203,10 +203,14 @@ def test_scheduler_pipelined_decode_matches_sync(tok, n_req, monkeypatch):
         assert sched.pipeline == (pipe == "1")
         done, evs = {}, [threading.Event() for _ in range(n_req)]
         try:
-            for i in range(n_req):
-                sched.submit(GenRequest(prompt_ids=tok.encode(f"req {i}"), max_tokens=[12, 7, 30][i],
-                                        json_mode=i != 1, min_tokens=[0, 0, 20][i],
-                                        on_done=lambda r, i=i: (done.__setitem__(i, r), evs[i].set())))
+            # all requests queued before the worker admits any: both runs decode the same batches (a free-text
+            # row's tokens from the fake engine depend on whether a JSON row shares its step), whatever the
+            # host's thread timing
+            with sched.cv:
+                for i in range(n_req):
+                    sched.submit(GenRequest(prompt_ids=tok.encode(f"req {i}"), max_tokens=[12, 7, 30][i],
+                                            json_mode=i != 1, min_tokens=[0, 0, 20][i],
+                                            on_done=lambda r, i=i: (done.__setitem__(i, r), evs[i].set())))
             for e in evs:
                 assert e.wait(10)
         finally:
