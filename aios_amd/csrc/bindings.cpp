@@ -288,6 +288,9 @@ PYBIND11_MODULE(_engine, m) {
       .def("tp_fuse_fits", &Engine::tp_fuse_fits)
       .def("set_kv_scales", &Engine::set_kv_scales)
       .def_property_readonly("kv_scales", &Engine::kv_scales)
+      .def("calibrate_kv_scales", &Engine::calibrate_kv_scales, py::arg("tokens"), py::arg("headroom") = 2.f,
+           py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("kv_amax", &Engine::kv_amax)
       .def_property_readonly("kv_fp8", &Engine::kv_fp8)
       .def("disable_tp_fuse", &Engine::disable_tp_fuse);
 
@@ -510,6 +513,9 @@ PYBIND11_MODULE(_engine, m) {
         py::arg("k_norm"), py::arg("eps"), py::arg("rope_neox"), py::arg("rope_base"), py::arg("pos"), py::arg("slot"),
         py::arg("q_out"), py::arg("k_cache"), py::arg("v_cache"), py::arg("max_ctx"), py::arg("st"),
         py::arg("block_table") = 0);
+  // host side of the fp8 KV calibration: observed table -> per-layer (K, V) scales
+  m.def("kv_scales_from_amax", &kv_scales_from_amax, py::arg("amax"), py::arg("n_layers"), py::arg("n_kv_heads"),
+        py::arg("headroom") = 2.f);
   m.def("sample",
         [](uintptr_t logits, int ldl, int B, int V, uintptr_t temperature, uintptr_t top_k, uint64_t seed,
            uintptr_t tokens, uintptr_t pos, uintptr_t mask, uintptr_t st, uintptr_t top_p, uintptr_t ts) {

@@ -46,8 +46,9 @@ struct EngineConfig {
   int vocab_parallel = 0;
   int device = 0;
   // KV cache element type: 0 = bf16, 1 = fp8 e4m3 (OCP) with a per-layer K / V scale (value = code x
-  // scale, Engine::set_kv_scales; 1.0 until set) -- half the cache bytes and the decode attention's
-  // K / V reads (bf16 or fp8 on MI355X)
+  // scale) -- half the cache bytes and the decode attention's K / V reads (bf16 or fp8
+  // on MI355X).  The scales are 1.0 until Engine::calibrate_kv_scales or set_kv_scales installs others;
+  // at 1.0 a layer whose keys / values leave e4m3's window (below 2^-9, above 448) is stored wrong
   int kv_fp8 = 0;
   // CU mask of the engine's stream (hipExtStreamCreateWithCUMask; 32 CUs per word, empty = every CU):
   // co-resident tiers each get their own CUs, and the engine sizes its grids to the mask's CU count
@@ -161,11 +162,23 @@ class Engine {
   std::vector<int> tp_fuse_fits();
   void disable_tp_fuse() { tp_fuse_ = nullptr; }
   // fp8 KV: the per-layer (K, V) scales, 2 x n_layers values (value = code x scale; captured decode
-  // graphs are dropped, they hold the old ones).  1.0 until set: e4m3 spans 2^-9 .. 448, the range of
-  // post-RoPE keys and values, as serving stacks' uncalibrated fp8 KV caches do; a calibrated model
-  // (per-layer K / V absolute maxima / 448) sets them here
+  // graphs are dropped, they hold the old ones).  1.0 until set, which is NOT adequate in general:
+  // at 1.0 e4m3 loses mantissa bits below 2^-6, flushes to zero below 2^-9 and saturates at 448, and a
+  // checkpoint's post-RoPE keys or its values can leave that window layer by layer.  The runtime
+  // loader therefore calibrates (calibrate_kv_scales) unless the config turns it off.
   void set_kv_scales(const std::vector<float>& s);
   std::vector<float> kv_scales() const { return kv_scale_; }
+  // fp8 KV calibration at load: prefill `tokens` into a free slot (throws when every slot holds
+  // blocks; nothing is evicted) with the KV writers' observer on -- every prefill path routes K / V
+  // through launch_qkv_post meanwhile -- which records max |value| per (layer, K / V, KV head) on the
+  // device.  Per layer: scale = max over heads x headroom / 448 (headroom 2: one e4m3 binade kept
+  // free for tokens the prompt did not contain); a layer that saw only zeros keeps 1.0, a non-finite
+  // maximum throws and names the layer.  The codes written meanwhile used the old scales: the slot is
+  // released again.  Installs the scales through set_kv_scales and returns them.  Static, per layer,
+  // from one prompt: no per-head or per-token scales.
+  std::vector<float> calibrate_kv_scales(const std::vector<int>& tokens, float headroom = 2.f);
+  // the table the last calibration observed, n_layers x 2 x n_kv_heads (empty before any)
+  std::vector<float> kv_amax() const { return kv_amax_; }
   int kv_fp8() const { return cfg_.kv_fp8; }
   bool vocab_parallel() const { return cfg_.vocab_parallel != 0; }
   void reset_graphs();
@@ -192,6 +205,10 @@ class Engine {
   int cus_ = 0;                          // CUs of the stream's mask (0: the whole device)
   int kv_es_ = 2;                        // bytes per KV element (2 bf16, 1 fp8)
   std::vector<float> kv_scale_;          // [n_layers][K, V] fp8 scales (value = code * scale)
+  std::vector<float> kv_amax_;           // [n_layers][K, V][n_kv_heads] of the last calibration
+  unsigned* d_kv_amax_ = nullptr;        // its device table (float bit patterns; fp8 engines only)
+  bool kv_obs_ = false;                  // calibration prefill running: observer on, K / V via qkv_post
+  unsigned* kv_obs_table(int l) const { return kv_obs_ ? d_kv_amax_ + (size_t)l * 2 * cfg_.n_kv_heads : nullptr; }
   bf16_t* kv_layer(bf16_t* base, int l) const {  // layer l's pool (element indices as bf16, bytes as kv_es_)
     return (bf16_t*)((char*)base + (size_t)l * layer_kv_elems_ * kv_es_);
   }

@@ -495,6 +495,7 @@ void Engine::finalize() {
   v_cache_ = (bf16_t*)dmalloc(kv_bytes_ / 2);
   HIP_CHECK(hipMemset(k_cache_, 0, kv_bytes_ / 2));
   HIP_CHECK(hipMemset(v_cache_, 0, kv_bytes_ / 2));
+  if (cfg_.kv_fp8) d_kv_amax_ = (unsigned*)dmalloc((size_t)cfg_.n_layers * 2 * Hkv * sizeof(unsigned));
   n_chunks_ = (cfg_.max_ctx + ATTN_CHUNK - 1) / ATTN_CHUNK;
   {
     const size_t nc = (size_t)std::max(prefill_rows_, Bm) * H;  // decode attention tickets [row][head]
@@ -1239,7 +1240,8 @@ void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_po
       // (>= 33 rows) only with AIOS_PREFILL_QKV_EPI=1 -- it needs S = 1 plans, and at 2048 tokens
       // the QKV GEMM then took 212.7 us against 115.7 (split-K) + 32 us of qkv_post (64 tokens:
       // 5.77 vs 4.6 ms per prompt), profiles/prefill_r5.txt
-      const bool qepi_ok = !cfg_.qk_norm && !cfg_.rope_neox && !L.bqkv && rope_cs_ && !tp;
+      // (calibration: K / V go through qkv_post, where the observer sits)
+      const bool qepi_ok = !cfg_.qk_norm && !cfg_.rope_neox && !L.bqkv && rope_cs_ && !tp && !kv_obs_;
       bool qepi = false;
       if (qepi_ok) {
         GemmQArgs q = g;
@@ -1262,6 +1264,7 @@ void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_po
       p.pos = gm_pos_; p.slot = gm_slot_; p.q_out = gm_q_;
       p.k_cache = kc; p.v_cache = vc; p.max_ctx = cfg_.max_ctx; p.block_table = d_bt_;
       kv_write_args(p, l);
+      p.amax = kv_obs_table(l);
       launch_qkv_post(p, stream_);
       }
       AttnPrefillArgs at;
@@ -1349,7 +1352,8 @@ std::vector<float> Engine::prefill(int slot, const std::vector<int>& tokens, int
           // QKV only (layer_decode runs the whole block; split it by temporarily faking)
           const LayerW& L = layers_[l];
           const int hd = cfg_.head_dim, qd = cfg_.n_heads * hd, kvd = cfg_.n_kv_heads * hd;
-          const bool fused_qkv = !cfg_.qk_norm && !cfg_.rope_neox;
+          // (calibration: EPI_STORE + qkv_post, where the observer sits)
+          const bool fused_qkv = !cfg_.qk_norm && !cfg_.rope_neox && !kv_obs_;
           int row0 = 0;
           for (auto& grp : qkv_groups(L)) {
             int nn = 0;
@@ -1389,6 +1393,7 @@ std::vector<float> Engine::prefill(int slot, const std::vector<int>& tokens, int
             kv_write_args(p, l);
             p.max_ctx = cfg_.max_ctx;
             p.block_table = d_bt_;
+            if (kv_obs_) { p.bias = L.bqkv; p.amax = kv_obs_table(l); }  // (the fused epilogue's bias)
             launch_qkv_post(p, stream_);
           }
         }
@@ -1805,6 +1810,62 @@ void Engine::set_kv_scales(const std::vector<float>& s) {
   if (finalized_) HIP_CHECK(hipStreamSynchronize(stream_));  // (no replay of the old graphs in flight)
   kv_scale_ = s;
   reset_graphs();
+}
+
+std::vector<float> kv_scales_from_amax(const std::vector<float>& amax, int n_layers, int n_kv_heads, float headroom) {
+  if (n_layers < 0 || n_kv_heads < 1 || amax.size() != (size_t)n_layers * 2 * n_kv_heads)
+    throw std::runtime_error("kv_scales_from_amax: need n_layers x 2 x n_kv_heads values");
+  if (!(headroom >= 1.f) || !std::isfinite(headroom)) throw std::runtime_error("kv_scales_from_amax: headroom must be >= 1");
+  std::vector<float> s((size_t)2 * n_layers, 1.f);
+  for (int l = 0; l < n_layers; ++l)
+    for (int kv = 0; kv < 2; ++kv) {
+      float m = 0.f;
+      for (int h = 0; h < n_kv_heads; ++h) {
+        const float v = amax[((size_t)l * 2 + kv) * n_kv_heads + h];
+        if (!std::isfinite(v))
+          throw std::runtime_error("fp8 KV calibration: non-finite " + std::string(kv ? "V" : "K") + " maximum in layer " +
+                                   std::to_string(l) + " (head " + std::to_string(h) + ")");
+        m = std::max(m, std::fabs(v));
+      }
+      const float sc = (m * headroom) / 448.f;
+      // (all zeros -- or a product that leaves fp32's range -- keeps 1.0: set_kv_scales wants positive finite values)
+      if (sc > 0.f && std::isfinite(sc)) s[(size_t)2 * l + kv] = sc;
+    }
+  return s;
+}
+
+std::vector<float> Engine::calibrate_kv_scales(const std::vector<int>& tokens, float headroom) {
+  if (!finalized_) throw std::runtime_error("calibrate_kv_scales: engine not finalized");
+  if (!cfg_.kv_fp8) throw std::runtime_error("calibrate_kv_scales: the KV cache is not fp8");
+  if (tokens.empty()) throw std::runtime_error("calibrate_kv_scales: empty prompt");
+  if (!(headroom >= 1.f) || !std::isfinite(headroom)) throw std::runtime_error("calibrate_kv_scales: headroom must be >= 1");
+  int slot = -1;
+  for (int s = 0; s < cfg_.max_slots && slot < 0; ++s) {
+    bool empty = true;
+    for (int j = 0; j < kv_maxb_; ++j) empty = empty && bt_[(size_t)s * kv_maxb_ + j] < 0;
+    if (empty) slot = s;
+  }
+  if (slot < 0) throw std::runtime_error("calibrate_kv_scales: no free slot (every slot holds KV blocks)");
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  const size_t n = (size_t)cfg_.n_layers * 2 * cfg_.n_kv_heads;
+  HIP_CHECK(hipMemsetAsync(d_kv_amax_, 0, n * sizeof(unsigned), stream_));
+  kv_obs_ = true;
+  try {
+    prefill(slot, tokens, 0, false);
+  } catch (...) {
+    kv_obs_ = false;
+    release_slot(slot);
+    throw;
+  }
+  kv_obs_ = false;
+  release_slot(slot);  // (the codes of this pass were written with the old scales)
+  std::vector<float> tab(n);
+  HIP_CHECK(hipMemcpyAsync(tab.data(), d_kv_amax_, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  kv_amax_ = tab;
+  const std::vector<float> s = kv_scales_from_amax(tab, cfg_.n_layers, cfg_.n_kv_heads, headroom);
+  set_kv_scales(s);
+  return s;
 }
 
 void Engine::reset_graphs() {

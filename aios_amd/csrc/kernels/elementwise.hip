@@ -146,9 +146,21 @@ void launch_swiglu_interleaved(const float* gu, int ldg, float* out, int ldo, in
   hipLaunchKernelGGL(swiglu_kernel, dim3(gx, rows), dim3(256), 0, st, gu, ldg, out, ldo, n);
 }
 
+// max over the wave's 64 lanes of float bit patterns compared as unsigned integers
+__device__ __forceinline__ unsigned wave_max_bits(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
+  return v;
+}
+
 // grid (T, n_heads + 2*n_kv_heads), one wave per head
 // one wave per (token, head): 4 waves per workgroup (round 5: one 64-thread workgroup per (token,
 // head) -- 98k of them for a 2048-token Mistral chunk -- ran 30.8 us, dispatch-bound)
+// OBS (fp8 calibration, QkvPostArgs::amax): every lane also keeps the largest |value| it stores to
+// the K / V cache as a bit pattern (integer max: a NaN's pattern is above every finite one and
+// survives), the wave reduces it and lane 0 issues one atomicMax on the head's table entry.  The
+// production instantiation (OBS = false) compiles to what it was before the observer existed.
+template <bool OBS>
 __global__ void __launch_bounds__(256) qkv_post_kernel(QkvPostArgs a) {
   const int nh = a.n_heads + 2 * a.n_kv_heads;
   const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -174,6 +186,7 @@ __global__ void __launch_bounds__(256) qkv_post_kernel(QkvPostArgs a) {
     s = wave_sum(s);
     inv = rsqrtf(s / (float)hd + a.eps);
   }
+  unsigned obs = 0;
   for (int p = lane; p < half; p += 64) {
     int ia, ib;
     if (part == 2) { ia = 2 * p; ib = 2 * p + 1; }
@@ -206,7 +219,14 @@ __global__ void __launch_bounds__(256) qkv_post_kernel(QkvPostArgs a) {
     } else {
       bf16_t* cache = part == 1 ? a.k_cache : a.v_cache;
       const size_t base = kv_offset(a.block_table, a.max_ctx / KV_BLOCK, slot, a.n_kv_heads, head, pos, hd);
+      if constexpr (OBS) obs = max(obs, max(__float_as_uint(fabsf(v0)), __float_as_uint(fabsf(v1))));
       kv_store_pair(cache, base + ia, base + ib, v0, v1, a.kv_fp8, part == 1 ? a.kv_inv_k : a.kv_inv_v);
+    }
+  }
+  if constexpr (OBS) {
+    if (part > 0) {  // (wave-uniform: every lane is back here after the pair loop)
+      obs = wave_max_bits(obs);
+      if (lane == 0) atomicMax(a.amax + (part - 1) * a.n_kv_heads + head, obs);
     }
   }
 }
@@ -215,7 +235,19 @@ __global__ void __launch_bounds__(256) qkv_post_kernel(QkvPostArgs a) {
 // head) kernel above ran a pos -> block-table -> store chain per wave and was latency bound: 30.8
 // us for a 2048-token Mistral chunk, ~3 TB/s of its 90 MB), then every thread walks row pairs
 // (2 floats in, RoPE, fp32 pair / bf16 pair out) with 8 in flight.
+// OBS: a thread's pairs lie 512 columns apart, so successive ones usually belong to different heads:
+// it keeps one (table entry, max) accumulator and flushes it with an LDS atomicMax when the entry
+// changes; the workgroup's [2][n_kv_heads] LDS table (dynamic shared memory, 8 * n_kv_heads bytes)
+// goes to the layer's table with one global atomicMax per entry.
+template <bool OBS>
 __global__ void __launch_bounds__(256) qkv_post_row_kernel(QkvPostArgs a) {
+  extern __shared__ unsigned obs_tab[];  // OBS only
+  int obs_key = -1;
+  unsigned obs = 0;
+  if constexpr (OBS) {
+    for (int i = threadIdx.x; i < 2 * a.n_kv_heads; i += 256) obs_tab[i] = 0;
+    __syncthreads();
+  }
   const int t = blockIdx.x;
   const int hd = a.head_dim, half = hd >> 1;
   const int qd = a.n_heads * hd, kvd = a.n_kv_heads * hd;
@@ -254,19 +286,37 @@ __global__ void __launch_bounds__(256) qkv_post_row_kernel(QkvPostArgs a) {
       } else {
         bf16_t* cache = part == 1 ? a.k_cache : a.v_cache;
         const size_t i0 = kvbase + (size_t)head * KV_BLOCK * hd + lr;
+        if constexpr (OBS) {
+          const int key = (part - 1) * a.n_kv_heads + head;
+          if (key != obs_key) {
+            if (obs_key >= 0) atomicMax(obs_tab + obs_key, obs);
+            obs_key = key;
+            obs = 0;
+          }
+          obs = max(obs, max(__float_as_uint(fabsf(v0)), __float_as_uint(fabsf(v1))));
+        }
         kv_store_pair(cache, i0, i0 + 1, v0, v1, a.kv_fp8, part == 1 ? a.kv_inv_k : a.kv_inv_v);
       }
     }
+  }
+  if constexpr (OBS) {
+    if (obs_key >= 0) atomicMax(obs_tab + obs_key, obs);
+    __syncthreads();  // (every thread arrives: the loops above only run out, nothing returns early)
+    for (int i = threadIdx.x; i < 2 * a.n_kv_heads; i += 256) atomicMax(a.amax + i, obs_tab[i]);
   }
 }
 
 void launch_qkv_post(const QkvPostArgs& a, hipStream_t st) {
   if (!a.rope_neox && !a.q_norm && !a.k_norm && !a.bias && a.rope_cs && a.head_dim % 2 == 0) {
-    hipLaunchKernelGGL(qkv_post_row_kernel, dim3(a.T), dim3(256), 0, st, a);
+    if (a.amax)
+      hipLaunchKernelGGL(qkv_post_row_kernel<true>, dim3(a.T), dim3(256), 2 * a.n_kv_heads * sizeof(unsigned), st, a);
+    else
+      hipLaunchKernelGGL(qkv_post_row_kernel<false>, dim3(a.T), dim3(256), 0, st, a);
     return;
   }
   const int items = a.T * (a.n_heads + 2 * a.n_kv_heads);
-  hipLaunchKernelGGL(qkv_post_kernel, dim3((items + 3) / 4), dim3(256), 0, st, a);
+  if (a.amax) hipLaunchKernelGGL(qkv_post_kernel<true>, dim3((items + 3) / 4), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(qkv_post_kernel<false>, dim3((items + 3) / 4), dim3(256), 0, st, a);
 }
 
 // ----------------------------------------------------------------------------------------------

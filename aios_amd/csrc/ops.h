@@ -87,8 +87,17 @@ struct QkvPostArgs {
   const int* block_table = nullptr;  // [slots][max_ctx / KV_BLOCK] or null (identity)
   int kv_fp8 = 0;    // fp8 e4m3 pool: code = value * kv_inv_{k,v}
   float kv_inv_k = 1.f, kv_inv_v = 1.f;
+  // fp8 calibration observer (null: off): the layer's [2][n_kv_heads] table of max |value| about to
+  // be stored (K row 0, V row 1; after bias / QK-norm / RoPE, before the fp8 conversion), kept as the
+  // bit patterns of the non-negative floats (they order like unsigned integers; a NaN sorts above
+  // every finite value and so stays visible) -- the launch takes the observing kernel variants
+  unsigned* amax = nullptr;
 };
 void launch_qkv_post(const QkvPostArgs& a, hipStream_t st);
+// fp8 KV calibration: per-layer (K, V) scales, 2 x n_layers values, from an observed table
+// amax[n_layers][2][n_kv_heads]: scale = max over heads x headroom / 448 (e4m3's largest finite
+// value); a layer / part that saw only zeros keeps 1.0; a non-finite entry throws, naming the layer
+std::vector<float> kv_scales_from_amax(const std::vector<float>& amax, int n_layers, int n_kv_heads, float headroom);
 
 // ---- attention ---------------------------------------------------------------------------------
 struct AttnDecodeArgs {

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import itertools
 import string
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 
@@ -110,7 +110,11 @@ def synthetic_bpe_vocab(n: int):
 
 
 def write_synthetic_gguf(path: str, cfg: ModelConfig, recipe: str = "Q4_K_M", seed: int = 0,
-                         weight_std: float = 0.02, vocab: Optional[tuple] = None) -> str:
+                         weight_std: float = 0.02, vocab: Optional[tuple] = None,
+                         tensor_scale: Optional[Dict[str, float]] = None) -> str:
+    """tensor_scale: tensor-name suffix -> multiplier applied to the drawn matrix before quantisation
+    (e.g. {"blk.0.attn_k.weight": 2.0 ** -10}; the first matching suffix wins).  The random stream does
+    not depend on it: a file written without it is byte-identical to one written before it existed."""
     rng = np.random.default_rng(seed)
     w = GGUFWriter(path)
     arch = cfg.arch
@@ -151,6 +155,10 @@ def write_synthetic_gguf(path: str, cfg: ModelConfig, recipe: str = "Q4_K_M", se
     def mat(name: str, rows: int, cols: int, layer: int, std: float):
         t = tensor_type(recipe, name, layer, cfg.n_layers)
         x = rng.standard_normal((rows, cols), dtype=np.float32) * std
+        for suffix, mul in (tensor_scale or {}).items():
+            if name.endswith(suffix):
+                x = x * np.float32(mul)
+                break
         w.add_tensor(name, (cols, rows), t, quantize(x, t))
 
     def vec(name: str, n: int, base: float = 1.0, amp: float = 0.1):

@@ -433,10 +433,22 @@ def spec_kv_dtype(path: str) -> str:
     return os.environ.get("AIOS_KV_DTYPE", "bf16")
 
 
+def spec_kv_calibrate(path: str) -> str:
+    """the '#...&kv=fp8_e4m3&kvcal=off' fragment of a model spec: "auto" (the default: an fp8 KV cache
+    is calibrated at load) or "off"; without effect on a bf16 KV cache"""
+    for kv in filter(None, path.partition("#")[2].split("&")):
+        k, _, v = kv.partition("=")
+        if k == "kvcal":
+            if v not in ("auto", "off"):
+                raise ValueError(f"kvcal must be 'auto' or 'off', not {v!r}")
+            return v
+    return "auto"
+
+
 def parse_spec(path: str):
     """'synthetic:<preset>[:<recipe>]#tp=N&q8=0' or '<file.gguf>#tp=N' -> (base, tp, act_q8).
     q8=0 selects fp32 activations in the GEMVs (int8 activations are the default); kv=fp8_e4m3 the
-    fp8 KV cache (spec_kv_dtype)."""
+    fp8 KV cache (spec_kv_dtype), kvcal=off its calibration off (spec_kv_calibrate)."""
     base, _, frag = path.partition("#")
     tp, q8 = 1, True
     for kv in filter(None, frag.split("&")):
@@ -478,6 +490,8 @@ def launch_tp(spec: str, world: int, devices, max_ctx: int, max_slots: int, max_
     from .ring import CommandRing
 
     devices = list(devices) or [0]
+    if kv_dtype != "bf16":
+        log.warning("%s: the fp8 KV cache of a tensor-parallel tier is uncalibrated (per-layer scales 1.0)", spec)
     ch = LeaderChannel(world)
     ring = CommandRing(world)
     procs = []

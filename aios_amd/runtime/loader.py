@@ -57,8 +57,16 @@ def shard_tensor(name: str, raw: np.ndarray, ggml_type: int, rows: int, cols: in
 
 def load_engine(path: str, max_ctx: Optional[int] = None, max_slots: int = 4, max_batch: int = 8, device: int = 0,
                 tp_rank: int = 0, tp_size: int = 1, name: Optional[str] = None, verbose: bool = False,
-                act_q8: bool = True, cu_mask: Optional[list] = None, kv_dtype: str = "bf16"):
-    """Load a GGUF file into a native Engine on `device`. Returns (engine, ModelConfig, reader)."""
+                act_q8: bool = True, cu_mask: Optional[list] = None, kv_dtype: str = "bf16", kv_calibrate=None):
+    """Load a GGUF file into a native Engine on `device`. Returns (engine, ModelConfig, reader).
+
+    kv_calibrate (fp8 KV cache only; ignored for bf16): None / "off" leaves the per-layer K / V scales
+    at 1.0, "auto" calibrates them on the built-in agent-style prompt in the model's own tokenizer, a
+    list of token ids calibrates on that list (runtime/kv_calibration.py).  A tensor-parallel shard
+    is not calibrated."""
+    from . import kv_calibration
+
+    kv_calibration.normalize_mode(kv_calibrate)  # (a bad value fails before the load, not after)
     m = native.require()
     t0 = time.time()
     r = GGUFReader(path)
@@ -74,6 +82,16 @@ def load_engine(path: str, max_ctx: Optional[int] = None, max_slots: int = 4, ma
         raw, rows, cols = shard_tensor(tname, raw, int(ti.ggml_type), rows, cols, tp_rank, tp_size, vp)
         eng.set_tensor(tname, int(ti.ggml_type), rows, cols, raw)
     finalize(eng)
+    if tp_size > 1:
+        if ec.kv_fp8 and kv_calibration.normalize_mode(kv_calibrate) != "off":
+            log.warning("%s: fp8 KV of a tensor-parallel shard is not calibrated (scales stay 1.0)", cfg.name)
+    else:
+        def tokenizer():
+            from .tokenizer import from_gguf
+
+            return from_gguf(r)
+
+        kv_calibration.calibrate(eng, kv_calibrate, tokenizer)
     if verbose:
         print(f"[loader] {cfg.name}: {eng.weight_bytes / 1e9:.2f} GB weights, {eng.kv_bytes / 1e9:.2f} GB KV, "
               f"{time.time() - t0:.1f}s")
@@ -109,9 +127,13 @@ def finalize(eng):
 def random_engine(cfg: ModelConfig, recipe: str = "Q4_K_M", seed: int = 0, max_ctx: Optional[int] = None,
                   max_slots: int = 4, max_batch: int = 8, device: int = 0, tp_rank: int = 0, tp_size: int = 1,
                   act_q8: bool = True, cu_mask: Optional[list] = None, kv_dtype: str = "bf16",
-                  stream_priority: int = 0):
+                  stream_priority: int = 0, kv_calibrate=None, tokenizer=None):
     """Engine with random-init weights of `cfg`'s architecture generated directly in HBM (cu_mask: the
-    CUs its stream may use, native.cu_mask_words)."""
+    CUs its stream may use, native.cu_mask_words).  kv_calibrate: as load_engine ("auto" needs
+    `tokenizer`, the synthetic model's tokenizer); the default leaves an fp8 KV cache uncalibrated."""
+    from . import kv_calibration
+
+    kv_calibration.normalize_mode(kv_calibrate)
     m = native.require()
     ec = native.engine_config(cfg, max_ctx=max_ctx or min(cfg.max_ctx, 4096), max_slots=max_slots,
                               max_batch=max_batch, device=device, tp_rank=tp_rank, tp_size=tp_size,
@@ -119,4 +141,6 @@ def random_engine(cfg: ModelConfig, recipe: str = "Q4_K_M", seed: int = 0, max_c
     eng = m.Engine(ec)
     eng.init_random(recipe, seed)
     finalize(eng)
+    if tp_size == 1:
+        kv_calibration.calibrate(eng, kv_calibrate, (lambda: tokenizer) if tokenizer is not None else None)
     return eng

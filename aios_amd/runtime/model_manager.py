@@ -187,12 +187,15 @@ class ModelManager:
         from .tokenizer import SpmTokenizer, from_gguf
 
         E = native.require()
-        from ..parallel.tp import launch_tp, parse_spec, spec_kv_dtype
+        from ..parallel.tp import launch_tp, parse_spec, spec_kv_calibrate, spec_kv_dtype
 
         device = self.device if m.device < 0 else m.device
 
         base, tp, act_q8 = parse_spec(m.path)
         kv_dtype = spec_kv_dtype(m.path)
+        # fp8 KV tiers are calibrated at load unless the spec says kvcal=off (no effect on bf16 KV;
+        # tensor-parallel tiers stay uncalibrated, launch_tp says so)
+        kv_calibrate = spec_kv_calibrate(m.path)
         faults = FaultSpec.from_env(m.name)
         if faults is not None:
             faults.check("load")
@@ -224,11 +227,11 @@ class ModelManager:
             cfg = get_preset(parts[1])
             recipe = parts[2] if len(parts) > 2 else "Q4_K_M"
             ctx = context_length or tier_context(cfg)
-            eng = random_engine(cfg, recipe, seed=_synth_seed(m.group or m.name), max_ctx=ctx,
-                                max_slots=self.max_slots, max_batch=self.max_batch, device=device, act_q8=act_q8,
-                                kv_dtype=kv_dtype)
             toks, scores, types = synthetic_vocab(cfg.vocab_size)
             tok = SpmTokenizer(toks, scores, types, cfg.bos_id, cfg.eos_id)
+            eng = random_engine(cfg, recipe, seed=_synth_seed(m.group or m.name), max_ctx=ctx,
+                                max_slots=self.max_slots, max_batch=self.max_batch, device=device, act_q8=act_q8,
+                                kv_dtype=kv_dtype, kv_calibrate=kv_calibrate, tokenizer=tok)
             tmpl = chat_template.for_model(cfg.chat_template if cfg.chat_template in chat_template.BUILTIN else "zephyr",
                                            tok)
         else:
@@ -236,7 +239,8 @@ class ModelManager:
                 raise FileNotFoundError(base)
             ctx = context_length or context_for_size(os.path.getsize(base))
             eng, cfg, reader = load_engine(base, max_ctx=ctx, max_slots=self.max_slots, max_batch=self.max_batch,
-                                           device=device, name=m.name, act_q8=act_q8, kv_dtype=kv_dtype)
+                                           device=device, name=m.name, act_q8=act_q8, kv_dtype=kv_dtype,
+                                           kv_calibrate=kv_calibrate)
             tok = from_gguf(reader)
             tmpl = chat_template.for_model(reader, tok)
         if not cpu:

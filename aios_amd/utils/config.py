@@ -46,6 +46,7 @@ class ModelTier:
     replicas: int = 1           # engines of this tier, one per GPU (request-level data parallelism)
     devices: List[int] = dataclasses.field(default_factory=list)  # GPUs of the replicas ([] = first `replicas` of models.devices)
     kv_dtype: str = "bf16"      # KV cache: "bf16" or "fp8_e4m3" (half the cache bytes; long contexts)
+    kv_calibrate: str = "auto"  # fp8 tiers only: "auto" = per-layer K / V scales from a calibration prefill at load, "off" = 1.0
 
 
 @dataclasses.dataclass
@@ -132,6 +133,8 @@ class NodeConfig:
                 frag.append("cpu")
             if t.kv_dtype and t.kv_dtype != "bf16":
                 frag.append(f"kv={t.kv_dtype}")
+                if t.kv_calibrate and t.kv_calibrate != "auto":
+                    frag.append(f"kvcal={t.kv_calibrate}")
             devs = list(t.devices)
             if not devs and t.replicas > 1:
                 devs = list(self.models.devices[:t.replicas]) or list(range(t.replicas))
@@ -168,6 +171,8 @@ class NodeConfig:
                 frag.append("cpu")
             if t.kv_dtype and t.kv_dtype != "bf16":
                 frag.append(f"kv={t.kv_dtype}")
+                if t.kv_calibrate and t.kv_calibrate != "auto":
+                    frag.append(f"kvcal={t.kv_calibrate}")
             out.append((name, path + ("#" + "&".join(frag) if frag else ""), t.context_length))
         return out
 
@@ -246,6 +251,11 @@ def load(path: Optional[str] = None, env=None) -> NodeConfig:
     for name, t in models_raw.items():
         if isinstance(t, dict):
             tiers[name] = _coerce(ModelTier, t, cfg_warn, f"models.{name}")
+            cal = tiers[name].kv_calibrate.strip().lower()
+            if cal not in ("auto", "off"):
+                cfg_warn.append(f"models.{name}.kv_calibrate: cannot use {tiers[name].kv_calibrate!r}; default kept")
+                cal = "auto"
+            tiers[name].kv_calibrate = cal
     models = _coerce(ModelsConfig, {k: v for k, v in models_raw.items() if not isinstance(v, dict)}, cfg_warn, "models")
     if isinstance(models_raw.get("devices"), list):
         models.devices = [int(x) for x in models_raw["devices"]]
