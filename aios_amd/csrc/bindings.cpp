@@ -222,6 +222,9 @@ PYBIND11_MODULE(_engine, m) {
            },
            py::arg("mask") = py::bytes())
       .def("decode_collect", &Engine::decode_collect, py::call_guard<py::gil_scoped_release>())
+      .def("set_sample_processors", &Engine::set_sample_processors, py::arg("min_p"), py::arg("repeat_penalty"),
+           py::arg("presence_penalty"), py::arg("frequency_penalty"), py::arg("recent"),
+           py::call_guard<py::gil_scoped_release>())
       .def("sample_first",
            [](Engine& e, int pos, float temperature, int top_k, float top_p, uint64_t seed, py::bytes mask) {
              std::string m = mask;
@@ -518,7 +521,9 @@ PYBIND11_MODULE(_engine, m) {
         py::arg("headroom") = 2.f);
   m.def("sample",
         [](uintptr_t logits, int ldl, int B, int V, uintptr_t temperature, uintptr_t top_k, uint64_t seed,
-           uintptr_t tokens, uintptr_t pos, uintptr_t mask, uintptr_t st, uintptr_t top_p, uintptr_t ts) {
+           uintptr_t tokens, uintptr_t pos, uintptr_t mask, uintptr_t st, uintptr_t top_p, uintptr_t ts,
+           uintptr_t min_p, uintptr_t pen_tokens, int pen_stride, uintptr_t repeat_penalty, uintptr_t presence_penalty,
+           uintptr_t frequency_penalty) {
           // grow-on-demand scratch for the raw-op binding (the engine owns its own)
           static void* ws = nullptr;
           static size_t ws_bytes = 0;
@@ -543,11 +548,15 @@ PYBIND11_MODULE(_engine, m) {
           a.tokens = (int*)tokens; a.pos = (int*)pos; a.mask = (const uint8_t*)mask;
           a.top_p = (const float*)top_p; a.ws = ws; a.ws_bytes = ws_bytes; a.counters = cnt;
           a.ts = (long long*)ts;
+          a.min_p = (const float*)min_p; a.pen_tokens = (const int*)pen_tokens; a.pen_stride = pen_stride;
+          a.repeat_penalty = (const float*)repeat_penalty; a.presence_penalty = (const float*)presence_penalty;
+          a.frequency_penalty = (const float*)frequency_penalty;
           launch_sample(a, S(st));
         },
         py::arg("logits"), py::arg("ldl"), py::arg("B"), py::arg("V"), py::arg("temperature"), py::arg("top_k"),
         py::arg("seed"), py::arg("tokens"), py::arg("pos"), py::arg("mask"), py::arg("st"), py::arg("top_p") = 0,
-        py::arg("ts") = 0);
+        py::arg("ts") = 0, py::arg("min_p") = 0, py::arg("pen_tokens") = 0, py::arg("pen_stride") = 0,
+        py::arg("repeat_penalty") = 0, py::arg("presence_penalty") = 0, py::arg("frequency_penalty") = 0);
   m.def("gemm",
         [](uintptr_t A, int lda, PyQMatrix* w, int M, uintptr_t C, int ldc, int accumulate, uintptr_t st) {
           GemmArgs a;

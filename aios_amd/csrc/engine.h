@@ -139,6 +139,17 @@ class Engine {
   void decode_sample(const std::vector<uint8_t>& mask);
   std::vector<int> decode_collect();
 
+  // Logit processors (ops.h SampleArgs: min-p, repeat / presence / frequency penalties) of the NEXT
+  // sampler launch only -- decode, decode_sample, sample_first or resample, whichever comes first --
+  // and dropped after it, so a row's values never reach another batch.  One entry per row of that
+  // launch; recent[b]: the row's penalty window, at most SAMPLE_PEN_MAX token ids, each in [0, vocab).
+  // decode() with processors staged replays the forward graph and enqueues the sampler eagerly, like
+  // the pipelined path (no graph of its own).  Single-GPU engines only: the ranks of a tensor-parallel
+  // engine sample in lock step from arguments this call does not broadcast.
+  void set_sample_processors(const std::vector<float>& min_p, const std::vector<float>& repeat_penalty,
+                             const std::vector<float>& presence_penalty, const std::vector<float>& frequency_penalty,
+                             const std::vector<std::vector<int>>& recent);
+
   // Device-resident greedy generation for benchmarking: runs n_steps decode steps for B
   // sequences without host synchronisation (tokens fed back on device, graph replay when
   // use_graph).  Sequences must already be prefilled to positions pos[b].
@@ -200,7 +211,13 @@ class Engine {
  private:
   void enqueue_decode_step(int B);       // uses device arrays d_tokens_/d_pos_/d_seqlen_/d_slot_
   void enqueue_decode_forward(int B);    // ... up to the logits (no sampler)
-  void enqueue_sample(int B);            // the step's sampler (sample_mask_: with d_mask_)
+  void enqueue_sample(int B, bool processors = false);  // the step's sampler (sample_mask_: with d_mask_)
+  // the staged logit processors of a B-row sampler launch: uploads them, points s at them and
+  // un-stages them (no-op when nothing is staged; throws when they were staged for another B)
+  void take_processors(SampleArgs& s, int B);
+  char* h_proc_ = nullptr;               // pinned staging: [4][max_batch] floats | [rows][stride] window ints
+  char* d_proc_ = nullptr;
+  int proc_rows_ = 0, proc_stride_ = 0;  // rows staged (0: none) and their window stride
   hipGraphExec_t forward_graph(int B);
   int cus_ = 0;                          // CUs of the stream's mask (0: the whole device)
   int kv_es_ = 2;                        // bytes per KV element (2 bf16, 1 fp8)

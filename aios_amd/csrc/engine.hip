@@ -102,6 +102,7 @@ Engine::~Engine() {
   if (h_par_) hipHostFree(h_par_);
   if (h_tok_out_) hipHostFree(h_tok_out_);
   if (h_mask_) hipHostFree(h_mask_);
+  if (h_proc_) hipHostFree(h_proc_);
   if (pipe_ev_) hipEventDestroy(pipe_ev_);
   if (stream_) hipStreamDestroy(stream_);
 }
@@ -546,6 +547,10 @@ void Engine::finalize() {
     // queued (decode_submit); the other paths use the first half
     HIP_CHECK(hipHostMalloc(&h_par_, 2 * par_bytes_, hipHostMallocDefault));
     HIP_CHECK(hipHostMalloc((void**)&h_mask_, mb, hipHostMallocDefault));
+    const size_t pb = (size_t)Bm * (4 * 4 + (size_t)SAMPLE_PEN_MAX * 4);  // logit processors (set_sample_processors)
+    HIP_CHECK(hipHostMalloc((void**)&h_proc_, pb, hipHostMallocDefault));
+    d_proc_ = (char*)dmalloc(pb);
+    ws += pb;
     HIP_CHECK(hipEventCreateWithFlags(&pipe_ev_, hipEventDisableTiming));
     HIP_CHECK(hipHostMalloc((void**)&h_tok_out_, (size_t)Bm * 4, hipHostMallocDefault));
     std::memset(h_par_, 0, 2 * par_bytes_);
@@ -1168,7 +1173,52 @@ void Engine::enqueue_decode_forward(int B) {
   nrm_lm_ = false;
 }
 
-void Engine::enqueue_sample(int B) {
+void Engine::set_sample_processors(const std::vector<float>& min_p, const std::vector<float>& repeat_penalty,
+                                   const std::vector<float>& presence_penalty,
+                                   const std::vector<float>& frequency_penalty,
+                                   const std::vector<std::vector<int>>& recent) {
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  if (cfg_.tp_size > 1) throw std::runtime_error("set_sample_processors: not available on a tensor-parallel engine");
+  const int B = (int)recent.size(), Bm = cfg_.max_batch;
+  if (B < 1 || B > Bm) throw std::runtime_error("set_sample_processors: batch out of range");
+  if ((int)min_p.size() != B || (int)repeat_penalty.size() != B || (int)presence_penalty.size() != B ||
+      (int)frequency_penalty.size() != B)
+    throw std::runtime_error("set_sample_processors: size mismatch");
+  int stride = 1;
+  for (const auto& w : recent) {
+    if ((int)w.size() > SAMPLE_PEN_MAX)
+      throw std::runtime_error("set_sample_processors: window longer than " + std::to_string(SAMPLE_PEN_MAX));
+    for (int t : w)
+      if (t < 0 || t >= cfg_.vocab_size) throw std::runtime_error("set_sample_processors: token out of range");
+    stride = std::max(stride, (int)w.size());
+  }
+  // (one pinned buffer, h_mask_'s rule: the previous processors' copy ran before the sampler whose
+  // token the host already collected -- the caller stages a step's processors from that token)
+  float* hf = (float*)h_proc_;
+  int* hw = (int*)(h_proc_ + (size_t)Bm * 16);
+  for (int b = 0; b < B; ++b) {
+    hf[b] = min_p[b]; hf[Bm + b] = repeat_penalty[b]; hf[2 * Bm + b] = presence_penalty[b];
+    hf[3 * Bm + b] = frequency_penalty[b];
+    for (int j = 0; j < stride; ++j) hw[(size_t)b * stride + j] = j < (int)recent[b].size() ? recent[b][j] : -1;
+  }
+  proc_rows_ = B;
+  proc_stride_ = stride;
+}
+
+void Engine::take_processors(SampleArgs& s, int B) {
+  if (!proc_rows_) return;
+  const int rows = proc_rows_, Bm = cfg_.max_batch;
+  proc_rows_ = 0;  // one shot, also when the launch does not happen
+  if (rows != B) throw std::runtime_error("sample processors staged for another batch size");
+  const size_t nbytes = (size_t)Bm * 16 + (size_t)B * proc_stride_ * 4;
+  HIP_CHECK(hipMemcpyAsync(d_proc_, h_proc_, nbytes, hipMemcpyHostToDevice, stream_));
+  const float* df = (const float*)d_proc_;
+  s.min_p = df; s.repeat_penalty = df + Bm; s.presence_penalty = df + 2 * Bm; s.frequency_penalty = df + 3 * Bm;
+  s.pen_tokens = (const int*)(d_proc_ + (size_t)Bm * 16);
+  s.pen_stride = proc_stride_;
+}
+
+void Engine::enqueue_sample(int B, bool processors) {
   const int V = cfg_.vocab_size;
   SampleArgs s;
   std::memset(&s, 0, sizeof(s));
@@ -1182,6 +1232,7 @@ void Engine::enqueue_sample(int B) {
   s.advance = 1;
   s.mask = sample_mask_ ? d_mask_ : nullptr;
   s.top_p = d_topp_; s.ws = sample_ws_; s.ws_bytes = sample_ws_bytes_; s.counters = sample_cnt_;
+  if (processors) take_processors(s, B);
   launch_sample(s, stream_);
 }
 
@@ -1481,6 +1532,10 @@ std::vector<int> Engine::decode(const std::vector<int>& slots, const std::vector
   if (!seeds.empty() && (int)seeds.size() != B) throw std::runtime_error("decode: seeds size mismatch");
   if (B < 1 || B > cfg_.max_batch) throw std::runtime_error("decode: batch out of range");
   if ((int)tokens.size() != B || (int)pos.size() != B) throw std::runtime_error("decode: size mismatch");
+  if (proc_rows_ && proc_rows_ != B) {  // (before the step changes any state)
+    proc_rows_ = 0;
+    throw std::runtime_error("decode: sample processors staged for another batch size");
+  }
   std::vector<int> sl(B);
   for (int b = 0; b < B; ++b) {
     if (pos[b] < 0 || pos[b] >= cfg_.max_ctx) throw std::runtime_error("decode: position out of range");
@@ -1513,7 +1568,24 @@ std::vector<int> Engine::decode(const std::vector<int>& slots, const std::vector
     nbytes = par_mask_off_ + mbytes;
   }
   HIP_CHECK(hipMemcpyAsync(d_par_, h_par_, nbytes, hipMemcpyHostToDevice, stream_));
-  decode_loop_run(B, 1, true);
+  if (proc_rows_) {
+    // staged logit processors: the forward graph and an eager sampler, as the pipelined path runs a
+    // step -- the captured (B, masked) step graphs never see them
+    for (int b = 0; b < B; ++b) {
+      kv_prepare_write(row_slots_[b], row_pos_[b], std::min(row_pos_[b] + 1, cfg_.max_ctx));
+      row_pos_[b] = std::min(row_pos_[b] + 1, cfg_.max_ctx);
+    }
+    kv_sync(B);
+    HIP_CHECK(hipGraphLaunch(forward_graph(B), stream_));
+    try {
+      enqueue_sample(B, true);
+    } catch (...) {
+      sample_mask_ = false;
+      throw;
+    }
+  } else {
+    decode_loop_run(B, 1, true);
+  }
   HIP_CHECK(hipMemcpyAsync(h_tok_out_, d_tokens_, B * 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
   sample_mask_ = false;
@@ -1551,6 +1623,7 @@ std::vector<int> Engine::resample(int B, const std::vector<float>& temperature, 
   s.tokens = d_tokens_; s.pos = d_pos_; s.advance = 0;
   s.mask = mask.empty() ? nullptr : d_mask_;
   s.top_p = d_topp_; s.ws = sample_ws_; s.ws_bytes = sample_ws_bytes_; s.counters = sample_cnt_;
+  take_processors(s, B);
   // pos was advanced by the step: RNG key uses pos[b] (a different stream than the first sample)
   launch_sample(s, stream_);
   std::vector<int> out(B);
@@ -1586,6 +1659,7 @@ int Engine::sample_first(int pos, float temperature, int top_k, float top_p, uin
   s.tokens = d_tokens_; s.pos = d_fpos_; s.advance = 0;
   s.mask = mask.empty() ? nullptr : d_mask_;
   s.top_p = d_topp_; s.ws = sample_ws_; s.ws_bytes = sample_ws_bytes_; s.counters = sample_cnt_;
+  take_processors(s, 1);
   launch_sample(s, stream_);
   int out = 0;
   HIP_CHECK(hipMemcpyAsync(&out, d_tokens_, 4, hipMemcpyDeviceToHost, stream_));
@@ -1759,7 +1833,12 @@ void Engine::decode_sample(const std::vector<uint8_t>& mask) {
     HIP_CHECK(hipMemcpyAsync(d_mask_, h_mask_, mbytes, hipMemcpyHostToDevice, stream_));
   }
   sample_mask_ = !mask.empty();
-  enqueue_sample(B);
+  try {
+    enqueue_sample(B, true);
+  } catch (...) {
+    sample_mask_ = false;
+    throw;
+  }
   sample_mask_ = false;
   HIP_CHECK(hipMemcpyAsync(h_tok_out_, d_tokens_, B * 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipEventRecord(pipe_ev_, stream_));

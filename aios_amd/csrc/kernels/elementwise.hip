@@ -368,6 +368,11 @@ __device__ ArgMax block_argmax(ArgMax m, float* sv, int* si) {
 //     Gumbel-max among the survivors; then advances pos / seq_len / history and re-arms.
 // Round 1 ran one 1024-thread workgroup per row over the whole vocabulary: 13-15 us per greedy
 // step, and 24 bisection passes re-reading the logits when sampling; top-p was ignored.
+// PROC (logit processors, SampleArgs::min_p / pen_tokens; the PROC = false instantiation is the kernel
+// without them): in A every slice workgroup counts the row's penalty window entries that fall in its
+// slice (an LDS table in s_ki, idle until the merge) and penalises its logits as it loads them, so the
+// slice argmax, the Gumbel path, the candidates and the merge's global max all see penalised logits;
+// min-p forces the candidate path and adds its ratio test to the merge's keep test.
 // ----------------------------------------------------------------------------------------------
 #ifndef AIOS_SAMPLE_PROBES
 #define AIOS_SAMPLE_PROBES 0
@@ -472,6 +477,9 @@ __device__ __forceinline__ int block_excl_scan(int c, int* s_w, int& total) {
   return off + x - c;
 }
 
+static_assert(SAMPLE_PEN_MAX <= SAMPLE_THREADS, "one penalty window entry per thread");
+static_assert(SAMPLE_MAX_V == 64 * SAMPLE_SLICE, "s_off holds 64 slices");
+template <bool PROC>
 __global__ void __launch_bounds__(SAMPLE_THREADS) sample_kernel(SampleArgs a) {
   __shared__ float sv[16];
   __shared__ int si[16];
@@ -496,7 +504,9 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_kernel(SampleArgs a) {
   if (a.seeds) seed = __hip_atomic_load(a.seeds + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else if (a.seed_dev) seed = __hip_atomic_load(a.seed_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const int rkey = a.seeds ? 0 : b;  // per-row seeds: row-independent streams
-  const bool filt = temp > 0.f && (topk > 0 || topp < 1.f);
+  float minp = 0.f;
+  if constexpr (PROC) minp = a.min_p ? a.min_p[b] : 0.f;
+  const bool filt = temp > 0.f && (topk > 0 || topp < 1.f || minp > 0.f);
   const int K = topk > 0 ? min(topk, SAMPLE_KCAP) : SAMPLE_TOPP_K;
   SampleWs w = sample_ws(a.ws, a.B, NS);
   // probe stamps (tools/sample_probe.py; compiled into probe builds only, AIOS_BUILD_PROBES=1: the sites'
@@ -509,11 +519,40 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_kernel(SampleArgs a) {
   // ---- A) this slice in registers
   float v[SAMPLE_PER_THREAD];
   ArgMax m{-INFINITY, 0x7fffffff};
+  bool pen = false;
+  float rp = 1.f, pp = 0.f, fp = 0.f;
+  if constexpr (PROC) {
+    pen = a.pen_tokens != nullptr;
+    if (pen) {  // per-token counts of the window entries inside this slice (pen_stride <= SAMPLE_THREADS)
+#pragma unroll
+      for (int j = 0; j < SAMPLE_PER_THREAD; ++j) s_ki[j * SAMPLE_THREADS + tid] = 0;
+      __syncthreads();
+      if (tid < a.pen_stride) {
+        const int t = a.pen_tokens[(size_t)b * a.pen_stride + tid];
+        const int o = t - slice * SAMPLE_SLICE;
+        if (t >= 0 && t < a.V && o >= 0 && o < SAMPLE_SLICE) atomicAdd(&s_ki[o], 1);
+      }
+      __syncthreads();
+      if (a.repeat_penalty) rp = a.repeat_penalty[b];
+      if (a.presence_penalty) pp = a.presence_penalty[b];
+      if (a.frequency_penalty) fp = a.frequency_penalty[b];
+    }
+  }
 #pragma unroll
   for (int j = 0; j < SAMPLE_PER_THREAD; ++j) {
     const int i = slice * SAMPLE_SLICE + j * SAMPLE_THREADS + tid;
     float x = -INFINITY;
     if (i < a.V && (!mask || ((mask[i >> 3] >> (i & 7)) & 1))) x = l[i];
+    if constexpr (PROC) {
+      if (pen) {
+        const int c = s_ki[j * SAMPLE_THREADS + tid];
+        if (c > 0 && x > -INFINITY) {
+          // (single roundings, no fused multiply-add: the host sampler's fp32 arithmetic, bit for bit)
+          x = x > 0.f ? __fdiv_rn(x, rp) : __fmul_rn(x, rp);
+          x = __fsub_rn(x, __fadd_rn(__fmul_rn((float)c, fp), pp));
+        }
+      }
+    }
     v[j] = x;
     m = am_better(m, ArgMax{x, i});
   }
@@ -617,6 +656,7 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_kernel(SampleArgs a) {
     // each survivor's rank-ordered mass before it sums over the S survivors only -- the old loop re-ran
     // exp over all nc candidates per survivor (~100 us per sampled token at nc ~ 2k, profiles/)
     const float it = 1.f / temp;
+    const float lmp = minp > 0.f ? logf(minp) : -INFINITY;  // min-p as (v - M) / T >= log(min_p)
     int c = 0;
 #pragma unroll
     for (int j = 0; j < SAMPLE_MAX_CAND / SAMPLE_THREADS; ++j) c += (cv[j] >= thr && cv[j] > -INFINITY) ? 1 : 0;
@@ -651,7 +691,8 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_kernel(SampleArgs a) {
       const float vu = s_sv[u];
       const int idx = s_si[u];
       bool keep = true;
-      if (topp < 1.f) {  // mass of the survivors ranked before this one (value desc, index asc)
+      if constexpr (PROC) keep = (vu - M) * it >= lmp;
+      if (keep && topp < 1.f) {  // mass of the survivors ranked before this one (value desc, index asc)
         // (float4 sweeps, four partial sums: the scalar loop waited one LDS round trip per survivor)
         float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
         for (int q = 0; q < S; q += 4) {
@@ -689,8 +730,14 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_kernel(SampleArgs a) {
 
 void launch_sample(const SampleArgs& a, hipStream_t st) {
   if (!a.ws || !a.counters) throw std::runtime_error("sample: workspace and counters required");
+  // (the merge's s_off holds 64 slices; no LDS grown for vocabularies nobody serves)
+  if (a.V < 1 || a.V > SAMPLE_MAX_V) throw std::runtime_error("sample: vocabulary outside 1.." + std::to_string(SAMPLE_MAX_V));
   if (a.ws_bytes < sample_ws_bytes(a.B, a.V)) throw std::runtime_error("sample: workspace too small");
-  hipLaunchKernelGGL(sample_kernel, dim3(sample_slices(a.V), a.B), dim3(SAMPLE_THREADS), 0, st, a);
+  if (a.pen_tokens && (a.pen_stride < 1 || a.pen_stride > SAMPLE_PEN_MAX))
+    throw std::runtime_error("sample: penalty window stride outside 1.." + std::to_string(SAMPLE_PEN_MAX));
+  const dim3 grid(sample_slices(a.V), a.B);
+  if (a.min_p || a.pen_tokens) hipLaunchKernelGGL(sample_kernel<true>, grid, dim3(SAMPLE_THREADS), 0, st, a);
+  else hipLaunchKernelGGL(sample_kernel<false>, grid, dim3(SAMPLE_THREADS), 0, st, a);
 }
 
 }  // namespace aios

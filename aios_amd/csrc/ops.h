@@ -154,6 +154,16 @@ bool attn_prefill_supports(int n_heads, int n_kv_heads, int head_dim);  // keys 
 // softmax(logits / T) restricted to the top-k (top_k[b] > 0, <= 256) and the nucleus top_p[b]
 // (< 1; over the top-256 when top-k is off)); then pos[b] += 1, seq_len[b] = pos[b] + 1,
 // history[b][step] = token.
+// Logit processors (min_p or pen_tokens non-null selects the kernel instantiation that has them), in
+// this order per row: penalties over the window pen_tokens[b] -- for every distinct token t with
+// c >= 1 occurrences, l[t] = l[t] > 0 ? l[t] / repeat_penalty : l[t] * repeat_penalty, then
+// l[t] -= c * frequency_penalty + presence_penalty (llama.cpp's rule) -- then the mask, then greedy
+// argmax, or top-k / top-p as above followed by min-p: a survivor i stays only if
+// exp((l_i - M) / T) >= min_p[b], M the largest allowed penalised logit (a ratio test on the tempered
+// distribution: it intersects with the nucleus, nothing is renormalised before it; <= 0: off; greedy
+// ignores it).  min-p with top-k and top-p both off works on the top-256 logits, like top-p alone.
+constexpr int SAMPLE_PEN_MAX = 256;  // longest penalty window (one entry per sampler thread)
+constexpr int SAMPLE_MAX_V = 262144; // largest vocabulary launch_sample takes (64 slices of 4096)
 struct SampleArgs {
   const float* logits;
   int ldl;
@@ -176,6 +186,12 @@ struct SampleArgs {
   size_t ws_bytes;
   int* counters;             // [B] arrival tickets, zero-initialised, self re-arming
   long long* ts;             // probe stamps [B][slices][16] (tools/sample_probe.py --stamps) or null
+  const float* min_p;              // [B] or null (off)
+  const float* repeat_penalty;     // [B] or null (1)
+  const float* presence_penalty;   // [B] or null (0)
+  const float* frequency_penalty;  // [B] or null (0)
+  const int* pen_tokens;           // [B][pen_stride] penalty windows, -1 = empty entry; or null
+  int pen_stride;                  // <= SAMPLE_PEN_MAX
 };
 void launch_sample(const SampleArgs& a, hipStream_t st);
 size_t sample_ws_bytes(int B, int V);

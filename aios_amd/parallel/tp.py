@@ -331,6 +331,10 @@ class TPEngine:
         self._closed = False
 
     def __getattr__(self, name):
+        if name == "set_sample_processors":
+            # not broadcast to the workers, whose samplers run in lock step with the leader's: a
+            # tensor-parallel tier has no logit processors (the scheduler logs that once)
+            raise AttributeError(name)
         attr = getattr(self._eng, name)
         if name not in self._FORWARD or not callable(attr):
             return attr
@@ -443,6 +447,21 @@ def spec_kv_calibrate(path: str) -> str:
                 raise ValueError(f"kvcal must be 'auto' or 'off', not {v!r}")
             return v
     return "auto"
+
+
+_SAMPLING_KEYS = {"minp": "min_p", "reppen": "repeat_penalty", "prespen": "presence_penalty",
+                  "freqpen": "frequency_penalty"}
+
+
+def spec_sampling(path: str) -> dict:
+    """the '#...&minp=0.05&reppen=1.1&prespen=0.2&freqpen=0.1' fragments of a model spec: the tier's
+    logit-processor defaults (Scheduler.sampling_defaults); only the ones present"""
+    out = {}
+    for kv in filter(None, path.partition("#")[2].split("&")):
+        k, _, v = kv.partition("=")
+        if k in _SAMPLING_KEYS:
+            out[_SAMPLING_KEYS[k]] = float(v)
+    return out
 
 
 def parse_spec(path: str):

@@ -44,6 +44,7 @@ class CpuEngine:
         c = model.cfg
         self.kv_bytes = 2 * c.n_layers * max_slots * max_ctx * c.n_kv_heads * c.head_dim * 4
         self.last: Optional[np.ndarray] = None
+        self._proc = None  # set_sample_processors: per-row processors of the next sampler call only
 
     @classmethod
     def from_gguf(cls, path: str, max_ctx: int = 2048, max_slots: int = 4, max_batch: int = 4,
@@ -82,10 +83,33 @@ class CpuEngine:
         self.last = logits[None]
         return logits if want_logits else []
 
+    def set_sample_processors(self, min_p, repeat_penalty, presence_penalty, frequency_penalty, recent):
+        """Per-row min-p, penalties and penalty windows (the rows' recent token ids) for the NEXT
+        sampler call (decode or sample_first), then dropped -- the native Engine's contract."""
+        B = len(recent)
+        if not (len(min_p) == len(repeat_penalty) == len(presence_penalty) == len(frequency_penalty) == B):
+            raise ValueError("set_sample_processors: size mismatch")
+        V = self.config.vocab_size
+        for w in recent:
+            if len(w) > host_sampler.PEN_MAX:
+                raise ValueError(f"set_sample_processors: window longer than {host_sampler.PEN_MAX}")
+            if any(t >= V for t in w):
+                raise ValueError("set_sample_processors: token out of range")
+        self._proc = (list(min_p), list(repeat_penalty), list(presence_penalty), list(frequency_penalty),
+                      [list(w) for w in recent])
+
+    def _sample(self, proc, b, logits, t, k, tp, m, rng):
+        if proc is None or b >= len(proc[4]):
+            return host_sampler.sample(logits, t, k, tp, m, rng)
+        mp, rp, pp, fp, recent = proc
+        logits = host_sampler.apply_penalties(logits, recent[b], rp[b], pp[b], fp[b])
+        return host_sampler.sample(logits, t, k, tp, m, rng, min_p=float(mp[b]))
+
     def decode(self, slots, toks, pos, temps, topk, seed, mask: bytes = b"", top_p=None, seeds=None):
         V = self.config.vocab_size
         row = (V + 7) // 8
         out, rows = [], []
+        proc, self._proc = self._proc, None
         for b, (slot, tok, p) in enumerate(zip(slots, toks, pos)):
             if p >= self.config.max_ctx:
                 raise ValueError("decode: position out of range")
@@ -99,7 +123,7 @@ class CpuEngine:
             rng = (np.random.default_rng([int(seeds[b]) & 0xFFFFFFFF, p]) if seeds else
                    np.random.default_rng((int(seed) << 20) ^ (slot << 12) ^ p))
             tp = float(top_p[b]) if top_p is not None and b < len(top_p) else 1.0
-            out.append(host_sampler.sample(logits, t, k, tp, m, rng))
+            out.append(self._sample(proc, b, logits, t, k, tp, m, rng))
         self.last = np.stack(rows) if rows else None
         return out
 
@@ -107,7 +131,8 @@ class CpuEngine:
         """the token after a prefill, from its last logits, with the decode steps' RNG stream"""
         logits = self.last[0]
         rng = np.random.default_rng([int(seed) & 0xFFFFFFFF, int(pos)])
-        return host_sampler.sample(logits, float(temperature), int(top_k), float(top_p), mask or None, rng)
+        proc, self._proc = self._proc, None
+        return self._sample(proc, 0, logits, float(temperature), int(top_k), float(top_p), mask or None, rng)
 
     def last_logits(self, B: int):
         return self.last[:B].reshape(-1) if self.last is not None else np.zeros(0, np.float32)

@@ -77,6 +77,7 @@ class FaultyEngine:
         return self._engine.decode(*a, **k)
 
     def __getattr__(self, name):
+        # every other attribute is the engine's own (set_sample_processors too: present iff it has it)
         attr = getattr(self._engine, name)
         if name == "decode_submit":  # the pipelined decode's step (present iff the engine has it)
             def submit(*a, **k):

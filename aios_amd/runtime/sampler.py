@@ -3,10 +3,16 @@
 Semantics match the device sampler (aios::sample_kernel): temperature <= 0 -> greedy argmax,
 else sample from softmax(logits / T) restricted to the top-k (if k > 0) and nucleus top-p (if
 0 < p < 1), always within the grammar's allowed-token bitmask when one is given.
+
+Logit processors, in the device sampler's order: `apply_penalties` (repeat / presence / frequency
+over a window of the row's recent tokens, llama.cpp's rule) before the mask and everything else;
+min-p after top-k / top-p: a survivor stays only while exp((l - M) / T) >= min_p, M the largest
+allowed (penalised) logit -- a ratio test on the tempered distribution, so it intersects with the
+nucleus instead of renormalising before it.  Greedy ignores min-p.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -16,17 +22,42 @@ def mask_to_bool(mask: bytes, vocab: int) -> np.ndarray:
     return bits[:vocab].astype(bool)
 
 
-def sample(logits: np.ndarray, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-           mask: Optional[bytes] = None, rng: Optional[np.random.Generator] = None) -> int:
+PEN_MAX = 256  # longest penalty window (the device sampler reads one window entry per thread)
+
+
+def penalty_window(repeat_last_n: int) -> int:
+    """the request field `repeat_last_n` as a window length: < 0 or > PEN_MAX clamp to PEN_MAX"""
+    n = int(repeat_last_n)
+    return PEN_MAX if n < 0 or n > PEN_MAX else n
+
+
+def apply_penalties(logits: np.ndarray, recent: Sequence[int], repeat_penalty: float = 1.0,
+                    presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> np.ndarray:
+    """Penalised copy of `logits`, in fp32 with the device sampler's operations.  For every distinct
+    token t with c >= 1 occurrences in `recent` (entries < 0 are empty):
+    l[t] = l[t] / repeat_penalty if l[t] > 0 else l[t] * repeat_penalty, then
+    l[t] -= c * frequency_penalty + presence_penalty."""
+    l = np.array(logits, dtype=np.float32)
+    ids = np.asarray([t for t in recent if 0 <= t < l.shape[0]], dtype=np.int64)
+    if ids.size == 0:
+        return l
+    toks, cnt = np.unique(ids, return_counts=True)
+    rp, pp, fp = np.float32(repeat_penalty), np.float32(presence_penalty), np.float32(frequency_penalty)
+    x = l[toks]
+    x = np.where(x > 0, x / rp, x * rp).astype(np.float32)
+    l[toks] = x - (cnt.astype(np.float32) * fp + pp)
+    return l
+
+
+def probabilities(logits: np.ndarray, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                  mask: Optional[bytes] = None, min_p: float = 0.0) -> np.ndarray:
+    """The distribution `sample` draws from at temperature > 0 (fp64): mask, top-k and nucleus top-p
+    on softmax(logits / T), then min-p."""
     l = np.asarray(logits, dtype=np.float64).copy()
     if mask is not None:
         allowed = mask_to_bool(mask, l.shape[0])
-        if not allowed.any():
-            return int(np.argmax(l))
-        l[~allowed] = -np.inf
-    if temperature <= 0.0:
-        return int(np.argmax(l))
-    rng = rng or np.random.default_rng()
+        if allowed.any():
+            l[~allowed] = -np.inf
     l = l / temperature
     if top_k and 0 < top_k < l.shape[0]:
         kth = np.partition(l, -top_k)[-top_k]
@@ -40,6 +71,23 @@ def sample(logits: np.ndarray, temperature: float = 0.0, top_k: int = 0, top_p: 
         cut = order[np.searchsorted(cum, top_p) + 1:]
         p[cut] = 0.0
         p /= p.sum()
+    if min_p > 0.0:  # (l is (logit - M) / T here: the log of the ratio to the best allowed token)
+        p[np.exp(l) < min_p] = 0.0
+        p /= p.sum()
+    return p
+
+
+def sample(logits: np.ndarray, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+           mask: Optional[bytes] = None, rng: Optional[np.random.Generator] = None, *, min_p: float = 0.0) -> int:
+    if temperature <= 0.0 or (mask is not None and not mask_to_bool(mask, len(logits)).any()):
+        l = np.asarray(logits, dtype=np.float64).copy()
+        if mask is not None:
+            allowed = mask_to_bool(mask, l.shape[0])
+            if allowed.any():
+                l[~allowed] = -np.inf
+        return int(np.argmax(l))
+    rng = rng or np.random.default_rng()
+    p = probabilities(logits, temperature, top_k, top_p, mask, min_p)
     return int(rng.choice(p.shape[0], p=p))
 
 

@@ -40,6 +40,9 @@ from . import sampler as host_sampler
 log = logging.getLogger("aios.runtime.scheduler")
 
 
+NEUTRAL_PROCESSORS = dict(min_p=0.0, repeat_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0)
+
+
 def _fresh_seed() -> int:
     return int.from_bytes(os.urandom(8), "little") | 1
 
@@ -56,6 +59,14 @@ class GenRequest:
     # plan length with it: random weights close a JSON object at arbitrary points)
     min_tokens: int = 0
     seed: int = 0
+    # logit processors (runtime/sampler.py: apply_penalties, min-p).  None = the tier's default
+    # (Scheduler.sampling_defaults, neutral unless the node config sets it); neutral values are
+    # min_p 0, repeat_penalty 1, presence_penalty 0, frequency_penalty 0
+    min_p: Optional[float] = None
+    repeat_penalty: Optional[float] = None
+    repeat_last_n: int = 64           # penalty window: the row's last n tokens, prompt tail included (< 0 or > 256: 256)
+    presence_penalty: Optional[float] = None
+    frequency_penalty: Optional[float] = None
     stop_ids: Optional[List[int]] = None
     on_delta: Optional[Callable[[str], None]] = None
     on_done: Optional[Callable[["GenResult"], None]] = None
@@ -79,7 +90,7 @@ class GenResult:
 
 class _Seq:
     __slots__ = ("req", "slot", "pos", "last", "out", "grammar_state", "emitted", "t_first", "cached", "todo",
-                 "p_off", "r_off", "seed")
+                 "p_off", "r_off", "seed", "proc", "pen_n")
 
     def __init__(self, req, slot):
         self.req, self.slot = req, slot
@@ -94,14 +105,24 @@ class _Seq:
         self.t_first = 0.0
         self.cached = 0
         self.todo: List[int] = []    # prompt tokens still to prefill
+        self.proc = None             # (min_p, repeat, presence, frequency penalty), None when all neutral
+        self.pen_n = 0               # penalty window length
         self.p_off = 0               # incremental detokenization window [p_off, r_off) already emitted
         self.r_off = 0
 
 
 class Scheduler:
     def __init__(self, engine, tokenizer, max_batch: int, max_slots: int, max_ctx: int, grammar=None,
-                 name: str = "model"):
+                 name: str = "model", sampling_defaults: Optional[Dict[str, float]] = None):
         self.engine = engine
+        # the tier's logit-processor defaults for requests that leave a field unset (the only way a
+        # gRPC caller, whose contract has no such fields, gets them)
+        self.sampling_defaults = dict(NEUTRAL_PROCESSORS)
+        for k, v in (sampling_defaults or {}).items():
+            if k not in NEUTRAL_PROCESSORS:
+                raise ValueError(f"unknown sampling default {k!r}")
+            self.sampling_defaults[k] = float(v)
+        self._warned_no_processors = False
         self.tok = tokenizer
         self.max_batch = max_batch
         self.max_ctx = max_ctx
@@ -254,6 +275,11 @@ class Scheduler:
         slot, common = self._pick_slot(ids)
         self.free_slots.remove(slot)
         seq = _Seq(r, slot)
+        d = self.sampling_defaults
+        proc = tuple(float(d[k] if getattr(r, k) is None else getattr(r, k)) for k in NEUTRAL_PROCESSORS)
+        if proc != tuple(NEUTRAL_PROCESSORS.values()):
+            seq.proc = proc
+            seq.pen_n = host_sampler.penalty_window(r.repeat_last_n)
         seq.cached = common
         seq.pos = common
         seq.todo = list(ids[common:])
@@ -297,11 +323,16 @@ class Scheduler:
         topp = float(r.top_p) if 0.0 < r.top_p < 1.0 else 1.0
         if hasattr(self.engine, "sample_first"):
             # on the device, the decode steps' sampler and RNG stream (seed, position)
+            self._processors([seq])
             tok = int(self.engine.sample_first(seq.pos - 1, float(r.temperature), topk, topp, seq.seed,
                                                bytes(mask) if mask is not None else b""))
         else:
             rng = np.random.default_rng([seq.seed & 0xFFFFFFFF, seq.pos - 1])
-            tok = host_sampler.sample(logits, r.temperature, r.top_k, r.top_p, mask, rng)
+            min_p = 0.0
+            if seq.proc is not None:
+                min_p = seq.proc[0]
+                logits = host_sampler.apply_penalties(logits, self._window(seq), *seq.proc[1:])
+            tok = host_sampler.sample(logits, r.temperature, r.top_k, r.top_p, mask, rng, min_p=min_p)
         seq.t_first = time.time()
         self.active.append(seq)
         self._accept(seq, tok)
@@ -431,6 +462,30 @@ class Scheduler:
                                   [float(s.req.top_p) if 0.0 < s.req.top_p < 1.0 else 1.0 for s in rows],
                                   [s.seed for s in rows])
 
+    @staticmethod
+    def _window(s: _Seq) -> List[int]:
+        """the row's penalty window: its last pen_n tokens, prompt tail included"""
+        n = s.pen_n
+        if n <= 0:
+            return []
+        return (s.req.prompt_ids[-(n - len(s.out)):] if len(s.out) < n else []) + s.out[-n:]
+
+    def _processors(self, rows):
+        """Before a sampler launch: hand the engine the rows' min-p / penalties and penalty windows
+        (every token of a row is on the host at this point).  All rows neutral: no call at all."""
+        if not any(s.proc is not None for s in rows):
+            return
+        setp = getattr(self.engine, "set_sample_processors", None)
+        if setp is None:
+            if not self._warned_no_processors:
+                self._warned_no_processors = True
+                log.warning("%s: the engine has no set_sample_processors; min_p and penalties are ignored", self.name)
+            return
+        neutral = tuple(NEUTRAL_PROCESSORS.values())
+        cols = list(zip(*[s.proc or neutral for s in rows]))
+        setp(list(cols[0]), list(cols[1]), list(cols[2]), list(cols[3]),
+             [self._window(s) if s.proc is not None else [] for s in rows])
+
     def _masks(self, rows) -> bytes:
         if not any(s.grammar_state is not None for s in rows):
             return b""
@@ -444,6 +499,7 @@ class Scheduler:
         if rows is None:  # a batch's first step (or after an admission / finish): host tokens
             rows = list(self.active)
             self._submit(rows, True)
+            self._processors(rows)
             self.engine.decode_sample(self._masks(rows))
         self._pending = None
         spec = self._can_speculate(rows)
@@ -456,6 +512,7 @@ class Scheduler:
         t2b = time.perf_counter()
         if spec and self.active == rows:
             # nobody finished or joined: sample the queued forward with the masks of the new tokens
+            self._processors(rows)
             self.engine.decode_sample(self._masks(rows))
             self._pending = rows
         # (spec and a row finished: the queued forward is dropped -- its KV writes at the next
@@ -484,6 +541,7 @@ class Scheduler:
                 self._full_mask = host_sampler.all_allowed(self.vocab)
             mask = b"".join(self._mask(s) if s.grammar_state is not None else self._full_mask for s in self.active)
         topp = [float(s.req.top_p) if 0.0 < s.req.top_p < 1.0 else 1.0 for s in self.active]
+        self._processors(self.active)
         t1 = time.perf_counter()
         out = self.engine.decode(slots, toks, pos, temps, topk, 0, mask, topp, seeds)
         t2 = time.perf_counter()

@@ -49,8 +49,20 @@ def _json_min_tokens(max_tokens: int) -> int:
     return max_tokens if v == "max" else min(max_tokens, int(v))
 
 
+# request-body fields of /v1/chat/completions that map onto GenRequest fields of the same name
+SAMPLING_FIELDS = {"top_p": float, "top_k": int, "seed": int, "min_p": float, "repeat_penalty": float,
+                   "presence_penalty": float, "frequency_penalty": float}
+
+
+def sampling_from_body(body: dict) -> dict:
+    """the sampling fields an OpenAI / llama-server client sent (absent or null ones stay the
+    request's and the tier's defaults)"""
+    return {k: cast(body[k]) for k, cast in SAMPLING_FIELDS.items() if body.get(k) is not None}
+
+
 async def generate(m, messages, max_tokens: int, temperature: float, json_mode: bool, on_delta=None,
-                   timeout: float = 120.0, seed: int = 0) -> GenResult:
+                   timeout: float = 120.0, seed: int = 0, sampling: Optional[dict] = None) -> GenResult:
+    """sampling: further GenRequest fields by name (top_p, top_k, seed, min_p, the penalties)"""
     loop = asyncio.get_running_loop()
     fut = loop.create_future()
     prompt = m.template.render(messages, add_generation_prompt=True)
@@ -65,6 +77,10 @@ async def generate(m, messages, max_tokens: int, temperature: float, json_mode: 
             loop.call_soon_threadsafe(on_delta, d)
     req = GenRequest(prompt_ids=ids, max_tokens=max_tokens, temperature=temperature, json_mode=json_mode,
                      min_tokens=_json_min_tokens(max_tokens) if json_mode else 0, seed=seed, on_delta=delta_cb, on_done=done, deadline=time.time() + timeout)
+    for k, v in (sampling or {}).items():
+        if k not in SAMPLING_FIELDS:
+            raise ValueError(f"unknown sampling field {k!r}")
+        setattr(req, k, v)
     m.scheduler.submit(req)
     try:
         return await asyncio.wait_for(fut, timeout + 5)
@@ -231,13 +247,19 @@ class AIRuntimeService:
         max_tokens = int(body.get("max_tokens") or 512)
         temperature = float(body.get("temperature", 0.7))
         json_mode = (body.get("response_format") or {}).get("type") == "json_object"
+        try:
+            sampling = sampling_from_body(body)
+        except (TypeError, ValueError) as e:
+            return web.json_response({"error": {"message": f"bad sampling field: {e}", "type": "invalid_request_error"}},
+                                     status=400)
         created = int(time.time())
         rid = f"chatcmpl-{created}{id(request) & 0xffff:04x}"
         if body.get("stream"):
             resp = web.StreamResponse(headers={"Content-Type": "text/event-stream"})
             await resp.prepare(request)
             q: asyncio.Queue = asyncio.Queue()
-            task = asyncio.ensure_future(generate(m, messages, max_tokens, temperature, json_mode, on_delta=q.put_nowait))
+            task = asyncio.ensure_future(generate(m, messages, max_tokens, temperature, json_mode, on_delta=q.put_nowait,
+                                                  sampling=sampling))
             task.add_done_callback(lambda _t: q.put_nowait(None))
             while True:
                 d = await q.get()
@@ -252,7 +274,7 @@ class AIRuntimeService:
             await resp.write(f"data: {json.dumps(end)}\n\ndata: [DONE]\n\n".encode())
             await resp.write_eof()
             return resp
-        res = await generate(m, messages, max_tokens, temperature, json_mode)
+        res = await generate(m, messages, max_tokens, temperature, json_mode, sampling=sampling)
         return web.json_response({
             "id": rid, "object": "chat.completion", "created": created, "model": m.name,
             "choices": [{"index": 0, "message": {"role": "assistant", "content": res.text},

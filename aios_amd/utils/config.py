@@ -47,6 +47,22 @@ class ModelTier:
     devices: List[int] = dataclasses.field(default_factory=list)  # GPUs of the replicas ([] = first `replicas` of models.devices)
     kv_dtype: str = "bf16"      # KV cache: "bf16" or "fp8_e4m3" (half the cache bytes; long contexts)
     kv_calibrate: str = "auto"  # fp8 tiers only: "auto" = per-layer K / V scales from a calibration prefill at load, "off" = 1.0
+    # the tier's logit-processor defaults for requests that do not set them (all neutral; llama-server's
+    # own min_p default is 0.05)
+    min_p: float = 0.0
+    repeat_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+
+    def sampling_frag(self) -> List[str]:
+        """the non-neutral processor defaults as model-spec fragments (parallel.tp.spec_sampling)"""
+        out = []
+        for key, field, neutral in (("minp", "min_p", 0.0), ("reppen", "repeat_penalty", 1.0),
+                                    ("prespen", "presence_penalty", 0.0), ("freqpen", "frequency_penalty", 0.0)):
+            v = float(getattr(self, field))
+            if v != neutral:
+                out.append(f"{key}={v!r}")
+        return out
 
 
 @dataclasses.dataclass
@@ -135,6 +151,7 @@ class NodeConfig:
                 frag.append(f"kv={t.kv_dtype}")
                 if t.kv_calibrate and t.kv_calibrate != "auto":
                     frag.append(f"kvcal={t.kv_calibrate}")
+            frag += t.sampling_frag()
             devs = list(t.devices)
             if not devs and t.replicas > 1:
                 devs = list(self.models.devices[:t.replicas]) or list(range(t.replicas))
@@ -173,6 +190,7 @@ class NodeConfig:
                 frag.append(f"kv={t.kv_dtype}")
                 if t.kv_calibrate and t.kv_calibrate != "auto":
                     frag.append(f"kvcal={t.kv_calibrate}")
+            frag += t.sampling_frag()
             out.append((name, path + ("#" + "&".join(frag) if frag else ""), t.context_length))
         return out
 
