@@ -9,6 +9,7 @@
 #include "comm.h"
 #include "rccl_comm.h"
 #include "engine.h"
+#include "gemv_desc.h"
 #include "grammar.h"
 #include "ops.h"
 
@@ -481,6 +482,45 @@ PYBIND11_MODULE(_engine, m) {
         py::arg("k_scale") = 1.f, py::arg("v_scale") = 1.f);
   m.def("attn_decode_split", &attn_decode_split);
   // physical identity of a device (PCI bus id): ranks that share a GPU see the same string
+  // the host-built launch descriptor of the one-workgroup-per-CU GEMVs (gemv_desc.h; no GPU needed):
+  // None when the shape cannot be split, else {"G", "g0", "np0", "racc_n", "wgs": [per-workgroup dicts]}
+  m.def("gemv_desc_build",
+        [](std::vector<int> qtypes, std::vector<int> rows, int K, int grid, int variant) -> py::object {
+          if (qtypes.empty() || qtypes.size() > 3 || rows.size() != qtypes.size())
+            throw std::runtime_error("gemv_desc_build: 1..3 segments");
+          GemvDescShape s{};
+          s.nseg = (int)qtypes.size();
+          int r = 0;
+          for (int k = 0; k < s.nseg; ++k) { s.qtype[k] = qtypes[k]; s.seg_row0[k] = r; r += rows[k]; }
+          s.N = r;
+          s.K = K;
+          s.grid = grid;
+          s.variant = variant;
+          CuPlan pl;
+          int G = 0;
+          if (!gemv_desc_plan(s, pl, G)) return py::none();
+          py::list wgs;
+          for (const GemvWgDesc& d : gemv_desc_build(s, pl, G)) {
+            py::dict w;
+            w["r0"] = d.r0; w["nrows"] = d.nrows; w["ngroups"] = d.ngroups; w["T"] = d.T; w["fmt1"] = d.fmt1;
+            w["nfast"] = d.nfast;
+            py::list pro;
+            for (int i = 0; i < GD_PRO; ++i) {
+              py::dict p;
+              p["off"] = d.pro[i] & ((1 << GD_OFF_BITS) - 1);
+              p["seg"] = (d.pro[i] >> GD_SEG_SHIFT) & 3;
+              p["fast"] = (d.pro[i] & GD_FAST) != 0;
+              p["seam"] = (d.pro[i] & GD_SEAM) != 0;
+              pro.append(p);
+            }
+            w["pro"] = pro;
+            wgs.append(w);
+          }
+          py::dict out;
+          out["G"] = G; out["g0"] = pl.g0; out["np0"] = pl.np0; out["racc_n"] = pl.racc_n; out["wgs"] = wgs;
+          return out;
+        },
+        py::arg("qtypes"), py::arg("rows"), py::arg("K"), py::arg("grid"), py::arg("variant") = 3);
   m.def("device_cu_count", [](int dev) {
     int n = 0;
     HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));

@@ -82,6 +82,7 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
   } else {
     HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   }
+  gemv_desc_reserve();  // the GEMV launch descriptors' device arena: allocated outside any graph capture
 
   layers_.resize(cfg_.n_layers);
   // B <= 8 decodes through the fused GEMVs; larger batches (up to 64) through the MFMA GEMM path

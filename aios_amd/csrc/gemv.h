@@ -68,6 +68,9 @@ struct GemvArgs {
 };
 
 void launch_gemv(const GemvArgs& a, hipStream_t st);
+// allocate the current device's arena of cached launch descriptors (gemv_desc.h) now: engines call it
+// at construction so that no allocation falls inside a graph capture
+void gemv_desc_reserve();
 bool gemv_engine_fits(const GemvArgs& a);  // the B-row LDS-DMA engine serves a (gemv_dispatch.hip)
 bool gemv_bf16_engine_fits(const GemvArgs& a);  // the BF16 LDS-DMA engine serves a (gemv_lds16.h)
 // EPI_TP_RESID through the row-pair kernel; false = nothing launched (gemv_dispatch.hip)

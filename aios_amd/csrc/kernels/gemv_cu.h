@@ -24,11 +24,36 @@
 constexpr int CU_WAVES = 16;
 constexpr int CU_THREADS = CU_WAVES * 64;
 
-struct CuPlan {
-  int g0;      // workgroups serving format-0 pairs [0, np0)
-  int np0;     // pairs of format 0; pairs [np0, N/2) use the last segment's format
-  int racc_n;  // LDS row accumulators: 2 x the most pairs any workgroup owns, rounded to 4
-};
+// (CuPlan and the per-workgroup records GemvWgDesc: gemv_desc.h)
+
+// this workgroup's launch descriptor: one 64-B scalar load (constant address space: the records are
+// written once on the host and never by a kernel)
+__device__ __forceinline__ GemvWgDesc gd_load(const GemvWgDesc* base) {
+  typedef int v16i __attribute__((ext_vector_type(16)));
+  using cp_t = const __attribute__((address_space(4))) v16i*;
+  const v16i v = *((cp_t)(uintptr_t)base + blockIdx.x);
+  GemvWgDesc d;
+  d.r0 = v[0]; d.nrows = v[1]; d.ngroups = v[2]; d.T = v[3]; d.fmt1 = v[4]; d.nfast = v[5];
+  d.rsv[0] = d.rsv[1] = 0;
+#pragma unroll
+  for (int i = 0; i < GD_PRO; ++i) d.pro[i] = v[8 + i];
+  return d;
+}
+
+// the launch side: what the descriptor of these args depends on
+inline GemvDescShape cu_desc_shape(const GemvArgs& a, int grid, int variant) {
+  GemvDescShape s{};
+  s.nseg = a.nseg;
+  for (int k = 0; k < a.nseg; ++k) {
+    s.qtype[k] = a.seg[k].qtype;
+    s.seg_row0[k] = a.seg_row0[k];
+  }
+  s.N = a.N;
+  s.K = a.K;
+  s.grid = grid;
+  s.variant = variant;
+  return s;
+}
 
 template <int CTRL>
 __device__ __forceinline__ float cu_dpp(float v) {
@@ -282,7 +307,6 @@ __global__ void __launch_bounds__(CU_THREADS) gemv_cu_b1(GemvArgs a, CuPlan pl) 
   constexpr int W = QFmt<QT0>::W, R = QFmt<QT0>::RUNS;
   const int nch = a.K / W;
   const int nit = (nch + 63) >> 6;
-  const int npairs = a.N >> 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   CU_STAMP(0);
@@ -291,22 +315,12 @@ __global__ void __launch_bounds__(CU_THREADS) gemv_cu_b1(GemvArgs a, CuPlan pl) 
       for (int i = 0; i < 8; ++i) a.dbg_ts[((size_t)blockIdx.x * 2 + (wave != 0)) * 8 + i] = ts[i];
   };
 
-  // ---- this workgroup's pair range
-  const int g = blockIdx.x;
-  const bool fmt1 = MIXED && g >= pl.g0;
-  int pb, pe;
-  if (!fmt1) {
-    const int np = MIXED ? pl.np0 : npairs, G = MIXED ? pl.g0 : (int)gridDim.x;
-    pb = (int)((long)g * np / G);
-    pe = (int)((long)(g + 1) * np / G);
-  } else {
-    const int np = npairs - pl.np0, G = (int)gridDim.x - pl.g0, gg = g - pl.g0;
-    pb = pl.np0 + (int)((long)gg * np / G);
-    pe = pl.np0 + (int)((long)(gg + 1) * np / G);
-  }
-  if (pb >= pe) return;  // whole workgroup, before any barrier
-  const int r0 = 2 * pb, nrows = 2 * (pe - pb);
-  const int items = nrows * nit;
+  // ---- this workgroup's rows (host-built descriptor, gemv_desc.h)
+  const GemvWgDesc d = gd_load(pl.desc);
+  if (d.nrows == 0) return;  // whole workgroup, before any barrier
+  const bool fmt1 = MIXED && d.fmt1;
+  const int r0 = d.r0, nrows = d.nrows;
+  const int items = d.ngroups;
   const int ipw = (items + CU_WAVES - 1) / CU_WAVES;
   const int j0 = __builtin_amdgcn_readfirstlane(min(items, wave * ipw));
   const int j1 = __builtin_amdgcn_readfirstlane(min(items, j0 + ipw));
@@ -374,17 +388,6 @@ inline size_t cu_lds_bytes(const GemvArgs& a, int racc_n) {
   return (64 + (size_t)racc_n) * 4 + (size_t)(a.K / W) * R * 8 + (size_t)a.K + 16;
 }
 
-inline int cu_fmt_bytes_per_256(int qt) {
-  switch (qt) {
-    case QT_Q4_K: return 144;
-    case QT_Q5_K: return 176;
-    case QT_Q6_K: return 210;
-    case QT_Q4_0: return 144;
-    case QT_Q8_0: return 272;
-  }
-  return 256;
-}
-
 // returns false when the shape does not fit (then the row-pair kernel runs)
 template <int QT0, int QT1>
 bool launch_gemv_cu(const GemvArgs& a, hipStream_t st) {
@@ -399,24 +402,15 @@ bool launch_gemv_cu(const GemvArgs& a, hipStream_t st) {
     }();
     const int mode = a.kernel_sel == 2 ? 8 : (a.kernel_sel == 0 ? env : 0);
     if (!mode || a.B != 1 || a.tune_dbg) return false;
-    const int npairs = a.N / 2;
-    const int cus = device_cu_count();
     // tune_grid > 0: that many workgroups (tests: ragged splits, > 64 pairs per workgroup)
-    const int G = std::min(a.tune_grid > 0 ? a.tune_grid : cus, npairs);
-    auto rup = [](int n, int g) { return (n + g - 1) / g; };
-    CuPlan pl{G, npairs, (2 * rup(npairs, G) + 3) & ~3};
-    if (QT0 != QT1 && a.nseg > 1) {
-      const int np0 = a.seg_row0[a.nseg - 1] / 2;
-      const double b0 = (double)np0 * cu_fmt_bytes_per_256(QT0), b1 = (double)(npairs - np0) * cu_fmt_bytes_per_256(QT1);
-      int g0 = (int)(G * b0 / (b0 + b1) + 0.5);
-      g0 = std::max(1, std::min(G - 1, g0));
-      if (G < 2 || np0 < 1 || np0 >= npairs) return false;
-      const int most = std::max(rup(np0, g0), rup(npairs - np0, G - g0));
-      pl = CuPlan{g0, np0, (2 * most + 3) & ~3};
-    }
+    const GemvDescShape sh = cu_desc_shape(a, a.tune_grid > 0 ? a.tune_grid : device_cu_count(), 2);
+    CuPlan pl;
+    int G;
+    if (!gemv_desc_plan(sh, pl, G)) return false;
     size_t lds = cu_lds_bytes<QT0, QT1>(a, pl.racc_n);
     if (lds > 160 * 1024) return false;
     lds = std::max(lds, (size_t)(81 * 1024));  // one workgroup per CU
+    pl.desc = gemv_desc_device(sh, pl, G);
     if (mode <= 4)
       hipLaunchKernelGGL((gemv_cu_b1<QT0, QT1, 4>), dim3(G), dim3(CU_THREADS), lds, st, a, pl);
     else

@@ -1,10 +1,85 @@
 // Host dispatcher: (segment-0 format, last-segment format) -> kernel instantiation.
+#include <array>
+#include <map>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 
 #include "../gemv.h"
+#include "../gemv_desc.h"
 
 namespace aios {
+
+// ---- launch descriptor cache (gemv_desc.h): process-wide, one arena list per device, nothing is
+// ever freed or moved, so a pointer handed to a captured graph stays valid for the process' life.
+// Allocation and upload run in relaxed capture mode on a private non-blocking stream: neither
+// touches a capturing stream, and a first use inside an engine's graph capture is legal.
+namespace {
+struct DescArena {
+  GemvWgDesc* dev = nullptr;
+  size_t cap = 0, used = 0;  // records
+};
+struct DescDevice {
+  std::vector<DescArena> arenas;
+  hipStream_t st = nullptr;
+  std::map<std::array<int, 14>, const GemvWgDesc*> cache;
+};
+std::mutex g_desc_mu;
+std::map<int, DescDevice> g_desc_dev;
+constexpr size_t DESC_ARENA_RECORDS = 32768;  // 2 MB: 128 whole-chip descriptors
+
+struct RelaxedCapture {  // this thread's capture mode -> relaxed for the scope
+  hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+  RelaxedCapture() { (void)hipThreadExchangeStreamCaptureMode(&mode); }
+  ~RelaxedCapture() { (void)hipThreadExchangeStreamCaptureMode(&mode); }
+};
+
+GemvWgDesc* desc_alloc(DescDevice& d, size_t n) {
+  if (d.arenas.empty() || d.arenas.back().used + n > d.arenas.back().cap) {
+    DescArena a;
+    a.cap = std::max(n, DESC_ARENA_RECORDS);
+    HIP_CHECK(hipMalloc((void**)&a.dev, a.cap * sizeof(GemvWgDesc)));
+    d.arenas.push_back(a);
+  }
+  DescArena& a = d.arenas.back();
+  GemvWgDesc* p = a.dev + a.used;
+  a.used += n;
+  return p;
+}
+}  // namespace
+
+void gemv_desc_reserve() {
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(g_desc_mu);
+  DescDevice& d = g_desc_dev[dev];
+  RelaxedCapture rc;
+  if (!d.st) HIP_CHECK(hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking));
+  if (d.arenas.empty()) {
+    desc_alloc(d, 1);
+    d.arenas.back().used = 0;
+  }
+}
+
+const GemvWgDesc* gemv_desc_device(const GemvDescShape& s, const CuPlan& pl, int G) {
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  // (g0 / np0 / G follow from the shape and the grid: the key needs only those)
+  const std::array<int, 14> key = {s.nseg, s.qtype[0], s.qtype[1], s.qtype[2], s.seg_row0[0], s.seg_row0[1],
+                                   s.seg_row0[2], s.N, s.K, s.grid, s.variant, G, pl.g0, pl.np0};
+  std::lock_guard<std::mutex> lk(g_desc_mu);
+  DescDevice& d = g_desc_dev[dev];
+  auto it = d.cache.find(key);
+  if (it != d.cache.end()) return it->second;
+  const std::vector<GemvWgDesc> host = gemv_desc_build(s, pl, G);
+  RelaxedCapture rc;
+  if (!d.st) HIP_CHECK(hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking));
+  GemvWgDesc* p = desc_alloc(d, host.size());
+  HIP_CHECK(hipMemcpyAsync(p, host.data(), host.size() * sizeof(GemvWgDesc), hipMemcpyHostToDevice, d.st));
+  HIP_CHECK(hipStreamSynchronize(d.st));
+  d.cache.emplace(key, p);
+  return p;
+}
 void gemv_q4k_q4k(const GemvArgs&, hipStream_t);
 void gemv_q4k_q6k(const GemvArgs&, hipStream_t);
 void gemv_q6k_q6k(const GemvArgs&, hipStream_t);

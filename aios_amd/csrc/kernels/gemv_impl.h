@@ -20,6 +20,7 @@
 #include "../comm.h"
 #include "../common.h"
 #include "../gemv.h"
+#include "../gemv_desc.h"
 #include "../qweight.h"
 
 namespace aios {

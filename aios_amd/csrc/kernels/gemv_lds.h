@@ -123,22 +123,15 @@ __device__ __forceinline__ void lg_vmcnt() {
 // and the loaders' issue rate, not HBM, set the step time).  General path (a slot crossing Q|K, or
 // the last slot): per-lane segment select and clamp.  Loader wave lw issues instructions lw,
 // lw + NL, ...; every loader issues exactly per_loader instructions per slot (exact counted waits).
+// the fast path: slot = groups [goff, goff + NGS) of segment `seg`, all inside the segment and the
+// workgroup's range.  Per plane one buffer resource, the slot's byte offset in an SGPR and
+// lane * width as the only VGPR; the padding instruction re-issues the slot's first piece of plane 0
+// into its own place.
 template <int QT>
-__device__ __forceinline__ void lg_dma_slot(const GemvArgs& a, uint8_t* dst, int s, int lw, int r0, int nit,
-                                            int ngroups) {
-  using L = LgLayout<QT>;  // (slot geometry only: identical for every RSUB)
+__device__ __forceinline__ void lg_dma_fast(const GemvArgs& a, uint8_t* dst, int seg, int goff, int lw) {
+  using L = LgLayout<QT>;
   using P = LgPlanes<QT>;
-  constexpr int NGS = L::NGS;
   const int lane = threadIdx.x & 63;
-  const int g0 = r0 * nit + s * NGS;            // global group index of the slot's first group
-  const int glast = r0 * nit + ngroups - 1;     // last group of the workgroup
-  const int G1 = a.nseg > 1 ? a.seg_row0[1] * nit : 0x7fffffff;
-  const int G2 = a.nseg > 2 ? a.seg_row0[2] * nit : 0x7fffffff;
-  const int gend = g0 + NGS - 1;
-  const int sg0 = g0 >= G2 ? 2 : (g0 >= G1 ? 1 : 0);
-  const int Gs = sg0 == 0 ? 0 : (sg0 == 1 ? G1 : G2);
-  const int Gn = sg0 == 0 ? G1 : (sg0 == 1 ? G2 : 0x7fffffff);
-  const bool fast = gend <= glast && gend < Gn;
   int issued = 0;
   int idx = 0;  // running instruction index over the planes
   static_for<4>([&](auto pc) {
@@ -149,37 +142,61 @@ __device__ __forceinline__ void lg_dma_slot(const GemvArgs& a, uint8_t* dst, int
       const uint8_t* pb0 = sgpr_ptr(lg_plane_ptr(a.seg[0], p));
       const uint8_t* pb1 = sgpr_ptr(lg_plane_ptr(a.seg[1], p));
       const uint8_t* pb2 = sgpr_ptr(lg_plane_ptr(a.seg[2], p));
-      if (fast) {
-        const __amdgpu_buffer_rsrc_t rs = mk_rsrc(sg0 == 0 ? pb0 : (sg0 == 1 ? pb1 : pb2));
-        const int soff0 = (g0 - Gs) * BPG;
+      const __amdgpu_buffer_rsrc_t rs = mk_rsrc(seg == 0 ? pb0 : (seg == 1 ? pb1 : pb2));
+      const int soff0 = goff * BPG;
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-          if ((idx + i) % LG_NL != lw) continue;
-          auto* ldst = (__attribute__((address_space(3))) void*)(dst + L::off(p) + i * 64 * S);
-          // (default policy instead of nt: +6-7 % on gate_up / down / lm_head, tools/gemv_cu_probe.py)
-          if constexpr (S == 16) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, ldst, 16, lane * 16, soff0 + i * 1024, 0, 2);
-          else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, ldst, 4, lane * 4, soff0 + i * 256, 0, 2 /* nt */);
-          ++issued;
-        }
-      } else {
-        // per-segment base shifted so that (group * BPG) indexes it directly
-        const uint64_t b0 = (uint64_t)pb0;
-        const uint64_t b1 = (uint64_t)pb1 - (uint64_t)(a.nseg > 1 ? G1 : 0) * BPG;
-        const uint64_t b2 = (uint64_t)pb2 - (uint64_t)(a.nseg > 2 ? G2 : 0) * BPG;
+      for (int i = 0; i < NI; ++i) {
+        if ((idx + i) % LG_NL != lw) continue;
+        auto* ldst = (__attribute__((address_space(3))) void*)(dst + L::off(p) + i * 64 * S);
+        // (default policy instead of nt: +6-7 % on gate_up / down / lm_head, tools/gemv_cu_probe.py)
+        if constexpr (S == 16) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, ldst, 16, lane * 16, soff0 + i * 1024, 0, 2);
+        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, ldst, 4, lane * 4, soff0 + i * 256, 0, 2 /* nt */);
+        ++issued;
+      }
+      if constexpr (p == 0) {
+        // pad to per_loader instructions (at most one: the loader with the odd instruction short)
+        if ((L::total_inst % LG_NL) != 0 && lw >= L::total_inst % LG_NL)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 16, lane * 16, soff0,
+                                                   0, 2);
+      }
+      idx += NI;
+    }
+  });
+  (void)issued;
+}
+
+// the general path (a slot crossing a segment seam, or the workgroup's last, clamped slot): per-lane
+// segment select and clamp
+template <int QT>
+__device__ __forceinline__ void lg_dma_general(const GemvArgs& a, uint8_t* dst, int g0, int glast, int G1, int G2,
+                                               int lw) {
+  using L = LgLayout<QT>;
+  using P = LgPlanes<QT>;
+  const int lane = threadIdx.x & 63;
+  int issued = 0;
+  int idx = 0;
+  static_for<4>([&](auto pc) {
+    constexpr int p = decltype(pc)::value;
+    if constexpr (p < P::n) {
+      constexpr int S = P::dsz[p], BPG = P::bpg[p];
+      constexpr int NI = L::ninst(p);
+      // per-segment base shifted so that (group * BPG) indexes it directly
+      const uint64_t b0 = (uint64_t)sgpr_ptr(lg_plane_ptr(a.seg[0], p));
+      const uint64_t b1 = (uint64_t)sgpr_ptr(lg_plane_ptr(a.seg[1], p)) - (uint64_t)(a.nseg > 1 ? G1 : 0) * BPG;
+      const uint64_t b2 = (uint64_t)sgpr_ptr(lg_plane_ptr(a.seg[2], p)) - (uint64_t)(a.nseg > 2 ? G2 : 0) * BPG;
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-          if ((idx + i) % LG_NL != lw) continue;
-          const int b = i * 64 * S + lane * S;  // byte within the plane's slot region
-          int g = g0 + b / BPG;                 // BPG is a power of two: a shift
-          const int o = b & (BPG - 1);
-          g = min(g, glast);                    // the last slot's tail and the padding lanes
-          const uint64_t base = g >= G2 ? b2 : (g >= G1 ? b1 : b0);
-          const uint8_t* src = (const uint8_t*)(base + (uint64_t)g * BPG + o);
-          auto* ldst = (__attribute__((address_space(3))) void*)(dst + L::off(p) + i * 64 * S);
-          if constexpr (S == 16) __builtin_amdgcn_global_load_lds((const void*)src, ldst, 16, 0, 2 /* nt */);
-          else __builtin_amdgcn_global_load_lds((const void*)src, ldst, 4, 0, 2 /* nt */);
-          ++issued;
-        }
+      for (int i = 0; i < NI; ++i) {
+        if ((idx + i) % LG_NL != lw) continue;
+        const int b = i * 64 * S + lane * S;  // byte within the plane's slot region
+        int g = g0 + b / BPG;                 // BPG is a power of two: a shift
+        const int o = b & (BPG - 1);
+        g = min(g, glast);                    // the last slot's tail and the padding lanes
+        const uint64_t base = g >= G2 ? b2 : (g >= G1 ? b1 : b0);
+        const uint8_t* src = (const uint8_t*)(base + (uint64_t)g * BPG + o);
+        auto* ldst = (__attribute__((address_space(3))) void*)(dst + L::off(p) + i * 64 * S);
+        if constexpr (S == 16) __builtin_amdgcn_global_load_lds((const void*)src, ldst, 16, 0, 2 /* nt */);
+        else __builtin_amdgcn_global_load_lds((const void*)src, ldst, 4, 0, 2 /* nt */);
+        ++issued;
       }
       idx += NI;
     }
@@ -195,6 +212,22 @@ __device__ __forceinline__ void lg_dma_slot(const GemvArgs& a, uint8_t* dst, int
     for (; issued < L::per_loader; ++issued)
       __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 2);
   }
+}
+
+template <int QT>
+__device__ __forceinline__ void lg_dma_slot(const GemvArgs& a, uint8_t* dst, int s, int lw, int r0, int nit,
+                                            int ngroups) {
+  constexpr int NGS = LgLayout<QT>::NGS;  // (slot geometry only: identical for every RSUB)
+  const int g0 = r0 * nit + s * NGS;            // global group index of the slot's first group
+  const int glast = r0 * nit + ngroups - 1;     // last group of the workgroup
+  const int G1 = a.nseg > 1 ? a.seg_row0[1] * nit : 0x7fffffff;
+  const int G2 = a.nseg > 2 ? a.seg_row0[2] * nit : 0x7fffffff;
+  const int gend = g0 + NGS - 1;
+  const int sg0 = g0 >= G2 ? 2 : (g0 >= G1 ? 1 : 0);
+  const int Gs = sg0 == 0 ? 0 : (sg0 == 1 ? G1 : G2);
+  const int Gn = sg0 == 0 ? G1 : (sg0 == 1 ? G2 : 0x7fffffff);
+  if (gend <= glast && gend < Gn) lg_dma_fast<QT>(a, dst, sg0, g0 - Gs, lw);
+  else lg_dma_general<QT>(a, dst, g0, glast, G1, G2, lw);
 }
 
 // consumer: the raw chunk of lane `lane` of group k from a ring slot
@@ -351,29 +384,19 @@ __global__ void __launch_bounds__(LG_THREADS) gemv_lds_b1(GemvArgs a, CuPlan pl)
   constexpr int W = QFmt<QT0>::W, R = QFmt<QT0>::RUNS;
   const int nch = a.K / W;
   const int nit = nch >> 6;
-  const int npairs = a.N >> 1;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const bool loader = wave >= LG_NG;
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   CU_STAMP(0);
 
-  // ---- this workgroup's pair range (as gemv_cu_b1)
-  const int g = blockIdx.x;
-  const bool fmt1 = MIXED && g >= pl.g0;
-  int pb, pe;
-  if (!fmt1) {
-    const int np = MIXED ? pl.np0 : npairs, G = MIXED ? pl.g0 : (int)gridDim.x;
-    pb = (int)((long)g * np / G);
-    pe = (int)((long)(g + 1) * np / G);
-  } else {
-    const int np = npairs - pl.np0, G = (int)gridDim.x - pl.g0, gg = g - pl.g0;
-    pb = pl.np0 + (int)((long)gg * np / G);
-    pe = pl.np0 + (int)((long)(gg + 1) * np / G);
-  }
-  if (pb >= pe) return;  // whole workgroup, before any barrier
-  const int r0 = 2 * pb, nrows = 2 * (pe - pb);
-  const int ngroups = nrows * nit;
+  // ---- this workgroup's rows, slot count and prologue slots: the host-built descriptor
+  // (gemv_desc.h), one scalar load instead of the split's 64-bit divisions in every wave
+  const GemvWgDesc d = gd_load(pl.desc);
+  if (d.nrows == 0) return;  // whole workgroup, before any barrier
+  const bool fmt1 = MIXED && d.fmt1;
+  const int r0 = d.r0, nrows = d.nrows;
+  const int ngroups = d.ngroups;
 
   // ---- LDS: red[64] | rowacc[B][racc_n] | ms [B][nch][R] | xq [B][nch][W] | ring [LG_R][slot]
   float* red = smem;
@@ -384,9 +407,6 @@ __global__ void __launch_bounds__(LG_THREADS) gemv_lds_b1(GemvArgs a, CuPlan pl)
   // address space and every ring read became a flat load waited with vmcnt)
   const int ring_off = (int)(((const uint8_t*)(xq + (size_t)B * a.K) - (const uint8_t*)smem + 255) & ~255);
   uint8_t* ring = (uint8_t*)smem + ring_off;
-  for (int i = threadIdx.x; i < B * pl.racc_n; i += LG_THREADS) rowacc[i] = 0.f;
-  if (threadIdx.x < 64) red[threadIdx.x] = 0.f;
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // ordered before B0
 
   // Loader and consumer paths are separate (no register merge between them: a phi of the
   // consumers' in-flight x registers made the compiler wait for them before the first barrier,
@@ -396,14 +416,33 @@ __global__ void __launch_bounds__(LG_THREADS) gemv_lds_b1(GemvArgs a, CuPlan pl)
     using L = LgLayout<QT, RSUB>;
     constexpr int PL = L::per_loader;
     constexpr int LG_R = L::R;
-    const int T = (ngroups + L::NGS - 1) / L::NGS;
+    static_assert(L::NGS == gd_slot_groups(QT), "the descriptor's slot count assumes this slot size");
+    static_assert(LG_R - 1 <= GD_PRO, "prologue slots described per workgroup");
+    const int T = d.T;
     const int lw = wave - LG_NG;
     // (an L2 prefetch of the slots past the ring -- one 4-B LDS-DMA per 128-B line, default
     // policy -- measured 25-30 % SLOWER on every shape, at any distance incl. the DMA'd slot
     // itself: the per-line requests double the CU's TA / L2 request count)
     if (LG_B0) lg_barrier();  // B0: the consumers' x loads are queued ahead of any weight byte
     const int npro = min(T, LG_R - 1);
-    for (int s = 0; s < npro; ++s) lg_dma_slot<QT>(a, ring + (size_t)s * L::slot_bytes, s, lw, r0, nit, ngroups);
+    if (d.nfast >= npro) {
+      // every prologue slot inside one segment (the descriptor says so and where): unrolled, the
+      // first slot's DMAs are the loader's first vector-memory instructions
+      static_for<LG_R - 1>([&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        if (s < npro) {
+          lg_dma_fast<QT>(a, ring + (size_t)s * L::slot_bytes, (d.pro[s] >> GD_SEG_SHIFT) & 3,
+                          d.pro[s] & ((1 << GD_OFF_BITS) - 1), lw);
+          if constexpr (s == 0) CU_STAMP(1);
+        }
+      });
+    } else {
+      for (int s = 0; s < npro; ++s) {
+        lg_dma_slot<QT>(a, ring + (size_t)s * L::slot_bytes, s, lw, r0, nit, ngroups);
+        if (s == 0) CU_STAMP(1);
+      }
+    }
+    CU_STAMP(2);
     if (npro == LG_R - 1) lg_vmcnt<(LG_R - 2) * PL>();
     else lg_vmcnt<0>();
     lg_barrier();  // B1: slot 0 landed, x staged
@@ -418,13 +457,20 @@ __global__ void __launch_bounds__(LG_THREADS) gemv_lds_b1(GemvArgs a, CuPlan pl)
       lg_barrier();
     }
     lg_barrier();  // final
+    // probes: loader wave 0's stamps (start, first slot's DMAs issued, prologue issued) go to the
+    // entries the consumers' two rows leave free
+    if (AIOS_GEMV_PROBES && a.dbg_ts && lane == 0 && lw == 0) {
+      a.dbg_ts[((size_t)blockIdx.x * 2 + 0) * 8 + 7] = ts[0];
+      a.dbg_ts[((size_t)blockIdx.x * 2 + 1) * 8 + 6] = ts[1];
+      a.dbg_ts[((size_t)blockIdx.x * 2 + 1) * 8 + 7] = ts[2];
+    }
   };
   auto consumer_path = [&](auto tag, float2& rope, int& pos0, int& kv_blk0) __attribute__((always_inline)) {
     constexpr int QT = decltype(tag)::value;
     using L = LgLayout<QT, RSUB>;
     constexpr int LG_R = L::R;
     constexpr int GPW = L::GPW;
-    const int T = (ngroups + L::NGS - 1) / L::NGS;
+    const int T = d.T;
     constexpr int NPF = 2;
     StagePre<NPF> pf{};
     q8_stage_prefetch(a, pf, threadIdx.x, LG_NG * 64);
@@ -666,16 +712,21 @@ __global__ void __launch_bounds__(LG_THREADS) gemv_lds_b1(GemvArgs a, CuPlan pl)
   };
   float2 rope = make_float2(1.f, 0.f);
   int pos0 = 0, kv_blk0 = 0;
+  // the loaders own the critical path (first weight byte requested): they go first and touch no
+  // LDS themselves; the consumers zero the accumulators (ordered before their use by B1)
   if (loader) {
     if (!fmt1) loader_path(FmtTag<QT0>{});
     else loader_path(FmtTag<QT1>{});
     return;
   }
+  for (int i = threadIdx.x; i < B * pl.racc_n; i += LG_NG * 64) rowacc[i] = 0.f;
+  if (threadIdx.x < 64) red[threadIdx.x] = 0.f;
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // ordered before B0
   if (!fmt1) consumer_path(FmtTag<QT0>{}, rope, pos0, kv_blk0);
   else consumer_path(FmtTag<QT1>{}, rope, pos0, kv_blk0);
   auto flush_ts = [&]() {
     if (a.dbg_ts && lane == 0 && (wave == 0 || wave == LG_NG - 1))
-      for (int i = 0; i < 8; ++i) a.dbg_ts[((size_t)blockIdx.x * 2 + (wave != 0)) * 8 + i] = ts[i];
+      for (int i = 0; i < (wave != 0 ? 6 : 7); ++i) a.dbg_ts[((size_t)blockIdx.x * 2 + (wave != 0)) * 8 + i] = ts[i];
   };
   if (wave != 0) {
     flush_ts();
@@ -783,19 +834,10 @@ bool launch_gemv_lds(const GemvArgs& a, hipStream_t st, bool dry = false) {
     constexpr int W = QFmt<QT0>::W, R = QFmt<QT0>::RUNS;
     const int nch = a.K / W;
     if (nch % 64) return false;
-    const int npairs = a.N / 2;
-    const int G = std::min(a.tune_grid > 0 ? a.tune_grid : device_cu_count(), npairs);
-    auto rup = [](int n, int g) { return (n + g - 1) / g; };
-    CuPlan pl{G, npairs, (2 * rup(npairs, G) + 3) & ~3};
-    if (QT0 != QT1 && a.nseg > 1) {
-      const int np0 = a.seg_row0[a.nseg - 1] / 2;
-      if (G < 2 || np0 < 1 || np0 >= npairs) return false;
-      const double b0 = (double)np0 * cu_fmt_bytes_per_256(QT0), b1 = (double)(npairs - np0) * cu_fmt_bytes_per_256(QT1);
-      int g0 = (int)(G * b0 / (b0 + b1) + 0.5);
-      g0 = std::max(1, std::min(G - 1, g0));
-      const int most = std::max(rup(np0, g0), rup(npairs - np0, G - g0));
-      pl = CuPlan{g0, np0, (2 * most + 3) & ~3};
-    }
+    const GemvDescShape sh = cu_desc_shape(a, a.tune_grid > 0 ? a.tune_grid : device_cu_count(), 3);
+    CuPlan pl;
+    int G;
+    if (!gemv_desc_plan(sh, pl, G)) return false;
     // small projections (O: <= ~40 KB per CU) stay on the row-pair kernel: the engine's fixed
     // start-up (first slot lands ~3-4 us after issue, behind the CU's whole prologue burst) and its
     // barrier steps cost more than the row kernel's x-staging stall there (tools/gemv_cu_probe.py:
@@ -819,6 +861,7 @@ bool launch_gemv_lds(const GemvArgs& a, hipStream_t st, bool dry = false) {
     }
     constexpr size_t LDS_MAX = 160 * 1024;
     size_t lds = 0;
+    if (!dry) pl.desc = gemv_desc_device(sh, pl, G);  // (cached: built on the first launch of the shape and grid)
     if (a.B == 1) {
       // AIOS_LDS_B1_RSUB (default 1): ring slots fewer than LgLayout's depth at batch 1.  A smaller
       // prologue burst (~64 instead of ~96 KB per CU, 16 MB chip-wide) lands the first slot sooner,

@@ -169,7 +169,14 @@ def main():
             phases = {"start": rel[:, 0, 0], "loads_issued": rel[:, 0, 1], "x_staged": rel[:, 0, 2],
                       "barrier": rel[:, 0, 3], "compute_w0": rel[:, 0, 4], "compute_w15": rel[:, 1, 4],
                       "final_barrier": rel[:, 0, 5], "epilogue": rel[:, 0, 6]}
+            if ssel == 3 and (t[:, 0, 7] > 0).all():
+                # loader wave 14's own stamps, and the fixed path as per-workgroup intervals
+                ld0, ld1, ld2 = rel[:, 0, 7], rel[:, 1, 6], rel[:, 1, 7]
+                phases.update({"loader_start": ld0, "loader_first_dma": ld1, "loader_prologue_issued": ld2,
+                               "d_start_to_first_dma": ld1 - ld0, "d_start_to_prologue_issued": ld2 - ld0,
+                               "d_last_slot_to_epilogue": rel[:, 0, 6] - np.maximum(rel[:, 0, 4], rel[:, 1, 4])})
         row["stamps_us"] = {k: [round(pct(v, q), 2) for q in (0, 50, 100)] for k, v in phases.items()}
+        row["stamps_p10_50_90_us"] = {k: [round(pct(v, q), 2) for q in (10, 50, 90)] for k, v in phases.items()}
         res.append(row)
         print(json.dumps(row), flush=True)
         del mats
