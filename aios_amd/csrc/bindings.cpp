@@ -10,6 +10,7 @@
 #include "rccl_comm.h"
 #include "engine.h"
 #include "gemv_desc.h"
+#include "gemv_plan.h"
 #include "grammar.h"
 #include "ops.h"
 
@@ -403,6 +404,7 @@ PYBIND11_MODULE(_engine, m) {
         [](std::vector<PyQMatrix*> segs, int B, uintptr_t x, int ldx, uintptr_t norm_w, float eps, uintptr_t y,
            int ldy, int epi, uintptr_t st, int force_v1, int act_q8, int tune_grid, int tune_u, int tune_ksplit, int tune_dbg,
            int kernel_sel, uintptr_t dbg_ts, uintptr_t x16, uintptr_t y16) {
+          (void)tune_ksplit;  // (accepted and ignored: no kernel has a K-split decomposition)
           GemvArgs a;
           std::memset(&a, 0, sizeof(a));
           a.nseg = (int)segs.size();
@@ -411,7 +413,7 @@ PYBIND11_MODULE(_engine, m) {
           a.N = r; a.K = segs[0]->w.cols; a.B = B;
           a.x = (const float*)x; a.ldx = ldx; a.norm_w = (const float*)norm_w; a.eps = eps;
           a.y = (float*)y; a.ldy = ldy; a.epi = epi; a.force_v1 = force_v1; a.act_q8 = act_q8;
-          a.tune_grid = tune_grid; a.tune_u = tune_u; a.tune_ksplit = tune_ksplit; a.tune_dbg = tune_dbg;
+          a.tune_grid = tune_grid; a.tune_u = tune_u; a.tune_dbg = tune_dbg;
           a.kernel_sel = kernel_sel; a.dbg_ts = (unsigned long long*)dbg_ts;
           a.x16 = (const bf16_t*)x16; a.y16 = (bf16_t*)y16;  // bf16 input / SwiGLU output (hand-off kernels)
           launch_gemv(a, S(st));
@@ -521,6 +523,55 @@ PYBIND11_MODULE(_engine, m) {
           return out;
         },
         py::arg("qtypes"), py::arg("rows"), py::arg("K"), py::arg("grid"), py::arg("variant") = 3);
+  // the launch plan of a GEMV (gemv_plan.h; no GPU needed, no HIP call): which kernel family, template
+  // parameters, grid, workgroup size and LDS bytes serve the shape on a device of `cus` CUs whose
+  // occupancy query answers `occupancy`.  Raises exactly where launch_gemv would.  knobs: GemvKnobs
+  // fields by name (the process environment is not read).  tp_fused: launch_gemv_tp_fused's plan
+  // (family "none": it would not launch).  "engine_fits" / "bf16_engine_fits": the engine's questions.
+  m.def("gemv_plan",
+        [](std::vector<int> qtypes, std::vector<int> rows, int K, int B, int epi, int act_q8, int force_v1,
+           int kernel_sel, int tune_grid, int tune_u, int tune_dbg, bool x16, bool y16, int grid_cap, int cus,
+           int occupancy, py::dict knobs, bool tp_fused, bool check) {
+          GemvShape s{};
+          s.nseg = (int)qtypes.size();
+          if (rows.size() != qtypes.size()) throw std::runtime_error("gemv_plan: one row count per segment");
+          if (s.nseg < 1 || s.nseg > GEMV_MAX_SEGS) throw std::runtime_error("gemv: bad segment count");  // (check = false too)
+          int r = 0;
+          for (int k = 0; k < s.nseg && k < GEMV_MAX_SEGS; ++k) {
+            s.qtype[k] = qtypes[k]; s.seg_row0[k] = r; s.seg_rows[k] = rows[k]; r += rows[k];
+          }
+          s.k_ok = 1; s.N = r; s.K = K; s.B = B; s.epi = epi; s.act_q8 = act_q8; s.force_v1 = force_v1;
+          s.kernel_sel = kernel_sel; s.tune_grid = tune_grid; s.tune_u = tune_u; s.tune_dbg = tune_dbg;
+          s.x16 = x16; s.y16 = y16; s.grid_cap = grid_cap;
+          GemvKnobs kn;
+          for (auto kv : knobs) {
+            const std::string name = py::cast<std::string>(kv.first);
+            int* f = name == "lds" ? &kn.lds : name == "lds_maxb" ? &kn.lds_maxb : name == "lds_b1_rsub" ? &kn.lds_b1_rsub
+                   : name == "lds_b1_rsub_q6" ? &kn.lds_b1_rsub_q6 : name == "cu" ? &kn.cu
+                   : name == "q8_balance" ? &kn.q8_balance : name == "bf16_lds" ? &kn.bf16_lds
+                   : name == "lb_cfg" ? &kn.lb_cfg : nullptr;
+            if (f) *f = py::cast<int>(kv.second);
+            else if (name == "lds_min_kb") kn.lds_min_kb = py::cast<double>(kv.second);
+            else throw std::runtime_error("gemv_plan: unknown knob " + name);
+          }
+          int asked = 0;
+          auto occ = [&](const GemvPlan&) { ++asked; return occupancy; };
+          const GemvPlan p = tp_fused ? plan_tp_fused(s, kn, cus, occ) : gemv_plan(s, kn, cus, occ, check);
+          py::dict d;
+          d["family"] = gemv_family_name(p.family);
+          d["B"] = p.B; d["U"] = p.U; d["PIPE"] = p.PIPE; d["RSUB"] = p.RSUB; d["R"] = p.R; d["GPW"] = p.GPW; d["D"] = p.D;
+          d["grid"] = p.grid; d["threads"] = p.threads; d["lds"] = p.lds; d["kt_max"] = p.kt_max;
+          d["occ_grid"] = p.occ_grid; d["occupancy_asked"] = asked;
+          d["g0"] = p.cu.g0; d["np0"] = p.cu.np0; d["racc_n"] = p.cu.racc_n;
+          d["engine_fits"] = gemv_engine_fits(s, kn, cus);
+          d["bf16_engine_fits"] = gemv_bf16_engine_fits(s, kn, cus);
+          return d;
+        },
+        py::arg("qtypes"), py::arg("rows"), py::arg("K"), py::arg("B"), py::arg("epi") = 0, py::arg("act_q8") = 1,
+        py::arg("force_v1") = 0, py::arg("kernel_sel") = 0, py::arg("tune_grid") = 0, py::arg("tune_u") = 0,
+        py::arg("tune_dbg") = 0, py::arg("x16") = false, py::arg("y16") = false, py::arg("grid_cap") = 0,
+        py::arg("cus") = 256, py::arg("occupancy") = 2, py::arg("knobs") = py::dict(), py::arg("tp_fused") = false,
+        py::arg("check") = true);
   m.def("device_cu_count", [](int dev) {
     int n = 0;
     HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));

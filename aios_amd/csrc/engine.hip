@@ -770,7 +770,7 @@ void Engine::allreduce(float* p, size_t n, float* residual) {
   }
 }
 
-// decode GEMV tuning knobs from the environment (read once): AIOS_GEMV_{U,GRID,KSPLIT}_{QKV,O,GU,DOWN,LM}
+// decode GEMV tuning knobs from the environment (read once): AIOS_GEMV_{U,GRID}_{QKV,O,GU,DOWN,LM}
 // -- in-situ sweeps of the captured decode step (tools/gemv_knob_sweep.sh); 0 = the launcher's choice
 static int gemv_knob(const char* what, const char* kind) {
   static std::map<std::string, int> cache;
@@ -785,7 +785,6 @@ static int gemv_knob(const char* what, const char* kind) {
 static void apply_knobs(GemvArgs& a, const char* kind) {
   a.tune_u = gemv_knob("U", kind);
   a.tune_grid = gemv_knob("GRID", kind);
-  a.tune_ksplit = gemv_knob("KSPLIT", kind);
 }
 
 void Engine::gemv(const std::vector<const QMat*>& segs, int N, int K, int B, const float* x, int ldx,
@@ -1101,7 +1100,6 @@ bool Engine::tp_fuse_gemv(GemvArgs a) {
   a.kernel_sel = 1;
   a.tune_grid = 0;
   a.tune_u = 0;
-  a.tune_ksplit = 0;
   a.grid_cap = tp_fuse_grid_;  // ranks sharing a GPU: every rank's workgroups resident together
   // (false: the row-pair kernel did not take it -- stage capacity within grid_cap, LDS plan -- and
   // nothing was launched; the caller runs the plain GEMV + all-reduce)

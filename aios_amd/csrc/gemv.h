@@ -1,4 +1,5 @@
-// Host-visible argument block for the fused decode GEMV (kernels/gemv.hip).
+// Host-visible argument block and entry points of the fused decode GEMVs (kernels/gemv_impl.h,
+// kernels/gemv_dispatch.hip; the launch choice: gemv_plan.h).
 #pragma once
 #include "common.h"
 #include "qweight.h"
@@ -27,9 +28,10 @@ struct GemvArgs {
   int kt_max;                   // K tile held in LDS (set by launch_gemv)
   int force_v1;                 // testing: bypass the persistent kernel
   int act_q8;                   // int8-quantised activations (v_dot4) for quantised weights
-  int tune_grid;                // blocks per CU override for the persistent kernels (0 = auto)
+  int tune_grid;                // grid override (0 = auto): workgroups per CU for the q8 row-pair kernel (which
+                                //   then also leaves its balanced launch), the whole grid for the
+                                //   one-workgroup-per-CU kernels (LDS engines, CU kernel)
   int tune_u;                   // chunks per lane per work item override (0 = auto; 1, 2, 4)
-  int tune_ksplit;              // -1 disables the K-split decomposition (testing / tuning)
   int tune_dbg;                 // microbenchmarks only: bit0 skip x staging, bit1 skip dot compute
   int kernel_sel;               // testing / probes: 0 = launcher's choice, 1 = row-pair int8 kernel,
                                 //   2 = CU register-streaming kernel, 3 = LDS-DMA engine
@@ -72,7 +74,7 @@ void launch_gemv(const GemvArgs& a, hipStream_t st);
 // at construction so that no allocation falls inside a graph capture
 void gemv_desc_reserve();
 bool gemv_engine_fits(const GemvArgs& a);  // the B-row LDS-DMA engine serves a (gemv_dispatch.hip)
-bool gemv_bf16_engine_fits(const GemvArgs& a);  // the BF16 LDS-DMA engine serves a (gemv_lds16.h)
+bool gemv_bf16_engine_fits(const GemvArgs& a);  // the BF16 LDS-DMA engine serves a (gemv_dispatch.hip)
 // EPI_TP_RESID through the row-pair kernel; false = nothing launched (gemv_dispatch.hip)
 bool launch_gemv_tp_fused(const GemvArgs& a, hipStream_t st);
 

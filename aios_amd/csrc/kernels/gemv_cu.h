@@ -40,21 +40,6 @@ __device__ __forceinline__ GemvWgDesc gd_load(const GemvWgDesc* base) {
   return d;
 }
 
-// the launch side: what the descriptor of these args depends on
-inline GemvDescShape cu_desc_shape(const GemvArgs& a, int grid, int variant) {
-  GemvDescShape s{};
-  s.nseg = a.nseg;
-  for (int k = 0; k < a.nseg; ++k) {
-    s.qtype[k] = a.seg[k].qtype;
-    s.seg_row0[k] = a.seg_row0[k];
-  }
-  s.N = a.N;
-  s.K = a.K;
-  s.grid = grid;
-  s.variant = variant;
-  return s;
-}
-
 template <int CTRL>
 __device__ __forceinline__ float cu_dpp(float v) {
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, false));
@@ -383,38 +368,11 @@ __global__ void __launch_bounds__(CU_THREADS) gemv_cu_b1(GemvArgs a, CuPlan pl) 
 }
 
 template <int QT0, int QT1>
-inline size_t cu_lds_bytes(const GemvArgs& a, int racc_n) {
-  constexpr int W = QFmt<QT0>::W, R = QFmt<QT0>::RUNS;
-  return (64 + (size_t)racc_n) * 4 + (size_t)(a.K / W) * R * 8 + (size_t)a.K + 16;
-}
-
-// returns false when the shape does not fit (then the row-pair kernel runs)
-template <int QT0, int QT1>
-bool launch_gemv_cu(const GemvArgs& a, hipStream_t st) {
-  if constexpr (!same_xlayout<QT0, QT1>) {
-    return false;
-  } else {
-    // register-streaming variant, kept for probes (kernel_sel 2 / AIOS_GEMV_CU=4|8): slower than the
-    // LDS-DMA engine (gemv_lds.h) because its weight stream stalls during the x staging
-    static const int env = [] {
-      const char* e = std::getenv("AIOS_GEMV_CU");
-      return e ? std::atoi(e) : 0;
-    }();
-    const int mode = a.kernel_sel == 2 ? 8 : (a.kernel_sel == 0 ? env : 0);
-    if (!mode || a.B != 1 || a.tune_dbg) return false;
-    // tune_grid > 0: that many workgroups (tests: ragged splits, > 64 pairs per workgroup)
-    const GemvDescShape sh = cu_desc_shape(a, a.tune_grid > 0 ? a.tune_grid : device_cu_count(), 2);
-    CuPlan pl;
-    int G;
-    if (!gemv_desc_plan(sh, pl, G)) return false;
-    size_t lds = cu_lds_bytes<QT0, QT1>(a, pl.racc_n);
-    if (lds > 160 * 1024) return false;
-    lds = std::max(lds, (size_t)(81 * 1024));  // one workgroup per CU
-    pl.desc = gemv_desc_device(sh, pl, G);
-    if (mode <= 4)
-      hipLaunchKernelGGL((gemv_cu_b1<QT0, QT1, 4>), dim3(G), dim3(CU_THREADS), lds, st, a, pl);
-    else
-      hipLaunchKernelGGL((gemv_cu_b1<QT0, QT1, 8>), dim3(G), dim3(CU_THREADS), lds, st, a, pl);
-    return true;
-  }
+void launch_gemv_cu(const GemvArgs& a, const GemvPlan& p, hipStream_t st) {
+  CuPlan pl = p.cu;
+  pl.desc = gemv_desc_device(p.desc, pl, p.grid);  // (cached: built on the first launch of the shape and grid)
+  if (p.D == 4)
+    hipLaunchKernelGGL((gemv_cu_b1<QT0, QT1, 4>), dim3(p.grid), dim3(p.threads), p.lds, st, a, pl);
+  else
+    hipLaunchKernelGGL((gemv_cu_b1<QT0, QT1, 8>), dim3(p.grid), dim3(p.threads), p.lds, st, a, pl);
 }

@@ -21,6 +21,7 @@
 #include "../common.h"
 #include "../gemv.h"
 #include "../gemv_desc.h"
+#include "../gemv_plan.h"
 #include "../qweight.h"
 
 namespace aios {
@@ -507,99 +508,97 @@ __global__ void __launch_bounds__(GP_THREADS) gemv_persistent(GemvArgs a) {
 }
 
 
-// returns false when the shape does not fit the persistent kernel's LDS budget
-template <int QT0, int QT1, int B, int U>
-bool launch_gemv_persistent(GemvArgs a, hipStream_t st) {
-  constexpr bool SEP = !same_xlayout<QT0, QT1>;
-  const size_t xfl = (size_t)B * a.K + (size_t)B * a.K / 16;
-  const size_t lds = (64 + xfl * (SEP ? 2 : 1) + 4) * sizeof(float);
-  if (lds > 96 * 1024) return false;
-  static int occ = -1;  // resident workgroups per CU for this instantiation (VGPR + LDS limited)
+
+// =============================================================================================
+// Launch side.  gemv_plan (gemv_plan.h) decides; what follows maps a plan's run-time parameters
+// onto the compiled instantiations and launches with the plan's grid, threads and LDS.
+// =============================================================================================
+static_assert(PLAN_V1_THREADS == GEMV_THREADS && PLAN_V1_ROWS_PER_BLOCK == GEMV_ROWS_PER_BLOCK &&
+                  PLAN_V1_LDS_FLOATS == GEMV_LDS_FLOATS && PLAN_GP_THREADS == GP_THREADS && PLAN_GP_WAVES == GP_WAVES &&
+                  PLAN_TPF_SLOTS == TPF_SLOTS && PLAN_TPF_CAP == TPF_CAP,
+              "gemv_plan.h mirrors the kernels' constants");
+
+// a kernel instantiation as a value (the *_visit functions hand one to a generic lambda)
+template <auto K>
+struct GemvKernel {
+  static constexpr auto fn = K;
+};
+
+// resident workgroups per CU of an instantiation (VGPR + LDS limited), asked once per instantiation
+template <class KT>
+int gemv_occupancy(KT, int threads, size_t lds) {
+  static int occ = -1;
   if (occ < 0) {
     int o = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, gemv_persistent<QT0, QT1, B, U>, GP_THREADS, lds) !=
-            hipSuccess || o <= 0)
-      o = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, KT::fn, threads, lds) != hipSuccess || o <= 0) o = 1;
     occ = o;
   }
-  const int per_cu = std::max(1, std::min(occ, (int)((160 * 1024) / lds)));
-  const int groups = (a.N / 2 + GP_WAVES - 1) / GP_WAVES;
-  const int blocks = std::min(groups, device_cu_count() * per_cu);
-  a.kt_max = a.K;
-  hipLaunchKernelGGL((gemv_persistent<QT0, QT1, B, U>), dim3(blocks), dim3(GP_THREADS), lds, st, a);
-  return true;
+  return occ;
 }
-
 
 #include "gemv_q8.h"
 #include "gemv_cu.h"
 #include "gemv_lds.h"
 #include "gemv_lds16.h"
 
-inline int qtype_block(int qt) {
-  return (qt == QT_Q4_K || qt == QT_Q5_K || qt == QT_Q6_K) ? 256 : (qt == QT_F16 || qt == QT_BF16 ? 8 : 32);
+template <int QT>
+constexpr bool plan_fmt_matches() {
+  return plan_w(QT) == QFmt<QT>::W && plan_runs(QT) == QFmt<QT>::RUNS;
+}
+static_assert(PLAN_Q8_WAVES == Q8_WAVES && PLAN_ONE_WG_THREADS == LG_THREADS && PLAN_ONE_WG_THREADS == CU_THREADS &&
+                  PLAN_LG_DBG_RING == LG_DBG_RING && plan_q8_max_threads(2, 1) == q8_max_threads<2, 1>() &&
+                  plan_q8_max_threads(3, 1) == q8_max_threads<3, 1>() && plan_q8_max_threads(1, 2) == q8_max_threads<1, 2>(),
+              "gemv_plan.h mirrors the kernels' constants");
+
+template <int QT0, int QT1, class F>
+auto gp_visit(const GemvPlan& p, F&& f) {  // persistent fp32: (B, U) = (1, 2), (2, 2), (4, 1)
+  if (p.B == 1) return f(GemvKernel<gemv_persistent<QT0, QT1, 1, 2>>{});
+  if (p.B == 2) return f(GemvKernel<gemv_persistent<QT0, QT1, 2, 2>>{});
+  return f(GemvKernel<gemv_persistent<QT0, QT1, 4, 1>>{});
 }
 
-template <int QT0, int QT1, int B, int U>
-void launch_gemv_t(GemvArgs a, hipStream_t st) {
-  const int blocks = (a.N + GEMV_ROWS_PER_BLOCK - 1) / GEMV_ROWS_PER_BLOCK;
-  int kt = (GEMV_LDS_FLOATS / B) / 256 * 256;
-  if (kt >= a.K) kt = a.K;
-  int blk = 8;
-  for (int s = 0; s < a.nseg; ++s) blk = std::max(blk, qtype_block(a.seg[s].qtype));
-  if (kt < blk) kt = blk;
-  a.kt_max = kt;
-  const size_t lds = (64 + (size_t)B * kt + (size_t)B * kt / 16 + 4) * sizeof(float);
-  hipLaunchKernelGGL((gemv_kernel<QT0, QT1, B, U>), dim3(blocks), dim3(GEMV_THREADS), lds, st, a);
+template <int QT0, int QT1, class F>
+auto v1_visit(const GemvPlan& p, F&& f) {  // v1 fp32: (B, U) = (1, 4), (1, 2), (2, 2), (4, 2), (8, 1)
+  if (p.B == 1 && p.U == 4) return f(GemvKernel<gemv_kernel<QT0, QT1, 1, 4>>{});
+  if (p.B == 1) return f(GemvKernel<gemv_kernel<QT0, QT1, 1, 2>>{});
+  if (p.B == 2) return f(GemvKernel<gemv_kernel<QT0, QT1, 2, 2>>{});
+  if (p.B == 4) return f(GemvKernel<gemv_kernel<QT0, QT1, 4, 2>>{});
+  return f(GemvKernel<gemv_kernel<QT0, QT1, 8, 1>>{});
 }
 
-// the fused TP all-reduce epilogue (EPI_TP_RESID, batch 1): the row-pair kernel or nothing
-template <int QT0>
-bool launch_gemv_tpf(const GemvArgs& a, hipStream_t st) {
-  if constexpr (QT0 == QT_F16 || QT0 == QT_BF16) {
-    return false;
-  } else {
-    if (a.B != 1 || !a.act_q8 || a.nseg != 1 || a.epi != EPI_TP_RESID) return false;
-    return launch_gemv_q8<QT0, QT0, 1>(a, st);
-  }
-}
-
+// The one entry point of a format pair (instantiated in gemv_kquant.hip, gemv_kquant2.hip and
+// gemv_legacy.hip, looked up through GEMV_PAIRS by gemv_dispatch.hip): plan the launch
+// (GEMV_TP_FUSED: as launch_gemv_tp_fused) and run it; GF_NONE: nothing launched.
 template <int QT0, int QT1>
-void launch_gemv_pair(const GemvArgs& a, hipStream_t st) {
-  constexpr int W = QFmt<QT0>::W;
-  const int chunks_per_lane = (a.K / W + 63) / 64;
-  constexpr bool Q8OK = QT0 != QT_F16 && QT0 != QT_BF16;
+GemvPlan gemv_pair(const GemvArgs& a, hipStream_t st, int flags) {
+  static_assert(plan_fmt_matches<QT0>() && plan_fmt_matches<QT1>() && same_xlayout<QT0, QT1> == plan_same_xlayout(QT0, QT1),
+                "gemv_plan.h mirrors the formats' constants");
+  constexpr bool Q8OK = !plan_is16(QT0);  // the int8-activation kernels exist for the quantised formats
+  auto occupancy = [](const GemvPlan& p) -> int {
+    if (p.family == GF_PERSISTENT)
+      return gp_visit<QT0, QT1>(p, [&](auto k) { return gemv_occupancy(k, GP_THREADS, p.lds); });
+    if constexpr (Q8OK)
+      return q8_visit<QT0, QT1>(p, [&](auto k) { return gemv_occupancy(k, Q8_WAVES * 64, p.lds); });
+    return 1;
+  };
+  const GemvShape s = gemv_shape(a);
+  const GemvPlan p = (flags & GEMV_TP_FUSED) ? plan_tp_fused(s, gemv_knobs(), device_cu_count(), occupancy)
+                                             : gemv_plan(s, gemv_knobs(), device_cu_count(), occupancy, false);  // (launch_gemv checked)
+  if (p.family == GF_NONE) return p;
+  GemvArgs b = a;
+  if (p.kt_max) b.kt_max = p.kt_max;
+  auto go = [&](auto k) { hipLaunchKernelGGL(k.fn, dim3(p.grid), dim3(p.threads), p.lds, st, b); };
   if constexpr (Q8OK) {
-    if (!a.force_v1 && a.act_q8) {
-      if (a.B <= 4 && launch_gemv_lds<QT0, QT1>(a, st)) return;  // B = 1..4: the LDS-DMA engine
-      if (a.B == 1 && launch_gemv_cu<QT0, QT1>(a, st)) return;
-      if (a.B == 1 && launch_gemv_q8<QT0, QT1, 1>(a, st)) return;
-      if (a.B == 2 && launch_gemv_q8<QT0, QT1, 2>(a, st)) return;
-      if (a.B > 2 && a.B <= 4 && launch_gemv_q8<QT0, QT1, 4>(a, st)) return;
-      if (a.B > 4 && launch_gemv_q8<QT0, QT1, 8>(a, st)) return;
-    }
+    if (p.family == GF_LDS) return launch_gemv_lds<QT0, QT1>(b, p, st), p;
+    if (p.family == GF_CU) return launch_gemv_cu<QT0, QT1>(b, p, st), p;
+    if (p.family == GF_Q8) return q8_visit<QT0, QT1>(p, go), p;
   }
   if constexpr (QT0 == QT_BF16 && QT1 == QT_BF16) {
-    if (!a.force_v1 && launch_gemv_lds16(a, st)) return;  // B = 1..4: the BF16 LDS-DMA engine
+    if (p.family == GF_LDS16) return launch_gemv_lds16(b, p, st), p;
   }
-  if (a.epi == EPI_TP_RESID)  // only the row-pair int8 kernel does the fused all-reduce epilogue
-    throw std::runtime_error("gemv: EPI_TP_RESID launch not taken by the row-pair kernel (use launch_gemv_tp_fused)");
-  if (a.x16 || a.y16) throw std::runtime_error("bf16 GEMV input / SwiGLU output: int8-activation kernels only");
-  if (!a.force_v1) {
-    if (a.B == 1 && launch_gemv_persistent<QT0, QT1, 1, 2>(a, st)) return;
-    if (a.B == 2 && launch_gemv_persistent<QT0, QT1, 2, 2>(a, st)) return;
-    if (a.B > 2 && a.B <= 4 && launch_gemv_persistent<QT0, QT1, 4, 1>(a, st)) return;
-  }
-  if (a.B == 1) {
-    if (chunks_per_lane >= 4) launch_gemv_t<QT0, QT1, 1, 4>(a, st);
-    else launch_gemv_t<QT0, QT1, 1, 2>(a, st);
-  } else if (a.B == 2) {
-    launch_gemv_t<QT0, QT1, 2, 2>(a, st);
-  } else if (a.B <= 4) {
-    launch_gemv_t<QT0, QT1, 4, 2>(a, st);
-  } else {
-    launch_gemv_t<QT0, QT1, 8, 1>(a, st);
-  }
+  if (p.family == GF_PERSISTENT) return gp_visit<QT0, QT1>(p, go), p;
+  if (p.family == GF_V1) return v1_visit<QT0, QT1>(p, go), p;
+  throw std::runtime_error("gemv: the plan's kernel family is not compiled for this format pair");
 }
 
 }  // namespace aios

@@ -795,127 +795,30 @@ __global__ void __launch_bounds__(LG_THREADS) gemv_lds_b1(GemvArgs a, CuPlan pl)
 }
 
 template <int QT>
-constexpr bool lg_supported() {
-  return QT == QT_Q4_K || QT == QT_Q5_K || QT == QT_Q6_K || QT == QT_Q4_0 || QT == QT_Q8_0;
+constexpr bool lg_plan_matches() {  // the plan's ring arithmetic (gemv_plan.h) is LgLayout's
+  return plan_lg_slot_bytes(QT) == LgLayout<QT, 0>::slot_bytes && plan_lg_depth(QT) == LgLayout<QT, 0>::R &&
+         LgLayout<QT, 1>::R == LgLayout<QT, 0>::R - 1 && LgLayout<QT, 2>::R == LgLayout<QT, 0>::R - 2;
 }
 
-// returns false when the shape does not fit (then the register kernels run)
-template <int QT0, int QT1, int B, int RSUB>
-size_t lg_lds_bytes(const GemvArgs& a, const CuPlan& pl) {
-  constexpr int W = QFmt<QT0>::W, R = QFmt<QT0>::RUNS;
-  const int nch = a.K / W;
-  const size_t head = (64 + (size_t)B * pl.racc_n) * 4 + (size_t)B * nch * R * 8 + (size_t)B * a.K;
-  const size_t ringb = std::max(LgLayout<QT0, RSUB>::R * LgLayout<QT0, RSUB>::slot_bytes,
-                                LgLayout<QT1, RSUB>::R * LgLayout<QT1, RSUB>::slot_bytes);
-  return (head + 255) / 256 * 256 + ringb;
-}
-
-// dry = true: only whether the engine WOULD serve these args (the engine's per-B path choice)
 template <int QT0, int QT1>
-bool launch_gemv_lds(const GemvArgs& a, hipStream_t st, bool dry = false) {
-  if constexpr (!same_xlayout<QT0, QT1> || !lg_supported<QT0>() || !lg_supported<QT1>()) {
-    return false;
-  } else {
-    // AIOS_GEMV_LDS: 0 = off, 1 = projections >= 96 KB per CU (default), 2 = every shape
-    static const int mode = [] {
-      const char* e = std::getenv("AIOS_GEMV_LDS");
-      return e ? std::atoi(e) : 1;
-    }();
-    // AIOS_GEMV_LDS_MAXB: batch rows the engine serves (1..4, default 4; whether B = 3 / 4 decode takes this path or the skinny MFMA GEMM is the
-    // engine's dec_gemm_min_b_, profiles/lds_batched_r3.txt)
-    static const int maxb = [] {
-      const char* e = std::getenv("AIOS_GEMV_LDS_MAXB");
-      return e ? std::max(1, std::min(4, std::atoi(e))) : 4;
-    }();
-    // (tune_dbg LG_DBG_RING: the probe's ring-only mode; every other microbenchmark bit -> row kernels)
-    if (!mode || a.B < 1 || a.B > (a.kernel_sel == 3 ? 4 : maxb) || (a.tune_dbg & ~LG_DBG_RING) ||
-        (a.kernel_sel != 0 && a.kernel_sel != 3))
-      return false;
-    constexpr int W = QFmt<QT0>::W, R = QFmt<QT0>::RUNS;
-    const int nch = a.K / W;
-    if (nch % 64) return false;
-    const GemvDescShape sh = cu_desc_shape(a, a.tune_grid > 0 ? a.tune_grid : device_cu_count(), 3);
-    CuPlan pl;
-    int G;
-    if (!gemv_desc_plan(sh, pl, G)) return false;
-    // small projections (O: <= ~40 KB per CU) stay on the row-pair kernel: the engine's fixed
-    // start-up (first slot lands ~3-4 us after issue, behind the CU's whole prologue burst) and its
-    // barrier steps cost more than the row kernel's x-staging stall there (tools/gemv_cu_probe.py:
-    // O 6.96 vs 5.60 us, QKV 8.73 vs 8.38; gate_up 17.35 vs 19.39, down 13.8 vs 15.2, lm_head 24.8
-    // vs 25.9).  AIOS_GEMV_LDS=2 forces the engine for every shape.
-    // batched launches (B >= 2) take the engine for every shape: the row-pair kernels re-read the
-    // B x vectors per wave and measured 2-3x slower there (B = 2 QKV 26 us vs 9.6 at B = 1)
-    if (mode != 2 && a.kernel_sel != 3 && a.B == 1) {
-      // AIOS_GEMV_LDS_MIN_KB: per-CU weight bytes from which the engine serves a shape.  Round 5
-      // (same box, tools/ab.sh): 40 instead of 96 -- the Mistral QKV (59 KB per CU) and the
-      // TinyLlama gate/up (50 KB) move to the engine: Mistral 668.2 / 668.1 -> 672.6 / 671.5 tok/s,
-      // TinyLlama 1500.7 / 1500.5 -> 1530.8 / 1535.3 (O, 37 KB, stays on the row kernel)
-      static const double min_kb = [] {
-        const char* e = std::getenv("AIOS_GEMV_LDS_MIN_KB");
-        return e ? std::atof(e) : 40.0;
-      }();
-      double bytes = 0;
-      for (int sg = 0; sg < a.nseg; ++sg)
-        bytes += (double)a.seg[sg].rows * a.K / 256.0 * cu_fmt_bytes_per_256(a.seg[sg].qtype);
-      if (bytes / G < min_kb * 1024) return false;
-    }
-    constexpr size_t LDS_MAX = 160 * 1024;
-    size_t lds = 0;
-    if (!dry) pl.desc = gemv_desc_device(sh, pl, G);  // (cached: built on the first launch of the shape and grid)
-    if (a.B == 1) {
-      // AIOS_LDS_B1_RSUB (default 1): ring slots fewer than LgLayout's depth at batch 1.  A smaller
-      // prologue burst (~64 instead of ~96 KB per CU, 16 MB chip-wide) lands the first slot sooner,
-      // and R - 1 slots in flight still cover the stream's latency: 649.4 -> 662.9 tok/s same box
-      // (tools/gpu_r4_ab5.sh, profiles/decode_mistral_rocprof_r4_final.txt)
-      static const int rsub_all = [] {
-        const char* e = std::getenv("AIOS_LDS_B1_RSUB");
-        return e ? std::atoi(e) : 1;
-      }();
-      // AIOS_LDS_B1_RSUB_Q6: Q6_K matrices' own value (default 2: their 23.5 KB slots cover the latency with
-      // one slot fewer still -- Mistral B=1 670.7 / 670.9 -> 672.6 / 672.0 tok/s, profiles/decode_b1_experiments_r6.txt)
-      static const int rsub_q6 = [] {
-        const char* e = std::getenv("AIOS_LDS_B1_RSUB_Q6");
-        return e ? std::atoi(e) : 2;
-      }();
-      const int rsub = (QT0 == QT_Q6_K && rsub_q6 >= 0) ? rsub_q6 : rsub_all;
-      if (rsub == 1 || rsub == 2) {
-        if (rsub == 1) lds = lg_lds_bytes<QT0, QT1, 1, 1>(a, pl);
-        else lds = lg_lds_bytes<QT0, QT1, 1, 2>(a, pl);
-        if (lds > LDS_MAX) return false;
-        if (dry) return true;
-        if (rsub == 1) hipLaunchKernelGGL((gemv_lds_b1<QT0, QT1, 1, 1>), dim3(G), dim3(LG_THREADS), lds, st, a, pl);
-        else hipLaunchKernelGGL((gemv_lds_b1<QT0, QT1, 1, 2>), dim3(G), dim3(LG_THREADS), lds, st, a, pl);
-        return true;
-      }
-      lds = lg_lds_bytes<QT0, QT1, 1, 0>(a, pl);
-      if (lds > LDS_MAX) return false;
-      if (dry) return true;
-      hipLaunchKernelGGL((gemv_lds_b1<QT0, QT1, 1, 0>), dim3(G), dim3(LG_THREADS), lds, st, a, pl);
-    } else if (a.B == 2) {
-      lds = lg_lds_bytes<QT0, QT1, 2, 1>(a, pl);
-      if (lds > LDS_MAX) return false;
-      if (dry) return true;
-      hipLaunchKernelGGL((gemv_lds_b1<QT0, QT1, 2, 1>), dim3(G), dim3(LG_THREADS), lds, st, a, pl);
-    } else if (a.B == 3) {  // its own instantiation: no idle fourth row in the dot work / staging
-      if ((lds = lg_lds_bytes<QT0, QT1, 3, 1>(a, pl)) <= LDS_MAX) {
-        if (dry) return true;
-        hipLaunchKernelGGL((gemv_lds_b1<QT0, QT1, 3, 1>), dim3(G), dim3(LG_THREADS), lds, st, a, pl);
-      } else {
-        lds = lg_lds_bytes<QT0, QT1, 3, 2>(a, pl);
-        if (lds > LDS_MAX) return false;
-        if (dry) return true;
-        hipLaunchKernelGGL((gemv_lds_b1<QT0, QT1, 3, 2>), dim3(G), dim3(LG_THREADS), lds, st, a, pl);
-      }
-    } else if ((lds = lg_lds_bytes<QT0, QT1, 4, 1>(a, pl)) <= LDS_MAX) {
-      if (dry) return true;
-      hipLaunchKernelGGL((gemv_lds_b1<QT0, QT1, 4, 1>), dim3(G), dim3(LG_THREADS), lds, st, a, pl);
-    } else {
-      // long K (the d_ff-wide down projection): four staged x rows leave room for a shallower ring
-      lds = lg_lds_bytes<QT0, QT1, 4, 2>(a, pl);
-      if (lds > LDS_MAX) return false;
-      if (dry) return true;
-      hipLaunchKernelGGL((gemv_lds_b1<QT0, QT1, 4, 2>), dim3(G), dim3(LG_THREADS), lds, st, a, pl);
-    }
-    return true;
+void launch_gemv_lds(const GemvArgs& a, const GemvPlan& p, hipStream_t st) {
+  static_assert(lg_plan_matches<QT0>() && lg_plan_matches<QT1>(), "gemv_plan.h: LDS engine ring");
+  CuPlan pl = p.cu;
+  pl.desc = gemv_desc_device(p.desc, pl, p.grid);  // (cached: built on the first launch of the shape and grid)
+#define LG_CASE(B, RSUB) \
+  case B * 10 + RSUB:    \
+    hipLaunchKernelGGL((gemv_lds_b1<QT0, QT1, B, RSUB>), dim3(p.grid), dim3(p.threads), p.lds, st, a, pl); \
+    break
+  switch (p.B * 10 + p.RSUB) {
+    LG_CASE(1, 0);
+    LG_CASE(1, 1);
+    LG_CASE(1, 2);
+    LG_CASE(2, 1);
+    LG_CASE(3, 1);
+    LG_CASE(3, 2);
+    LG_CASE(4, 1);
+    LG_CASE(4, 2);
+    default: throw std::runtime_error("gemv: no LDS engine instantiation for the plan");
   }
+#undef LG_CASE
 }

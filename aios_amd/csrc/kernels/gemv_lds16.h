@@ -304,64 +304,25 @@ __global__ void __launch_bounds__(LG_THREADS) gemv_lds16(GemvArgs a, CuPlan pl) 
   }
 }
 
-template <int B, int R, int GPW = 2>
-size_t lb_lds_bytes(const GemvArgs& a, const CuPlan& pl) {
-  const size_t head = (64 + (size_t)B * pl.racc_n) * 4 + (size_t)B * a.K * 2;
-  return (head + 255) / 256 * 256 + (size_t)R * LbSlot<GPW>::BYTES;
-}
-
-// The BF16 engine for B = 1..4, or false (shape / epilogue outside it: the register kernels run).
-// dry = true: only whether it would serve these args.
-inline bool launch_gemv_lds16(const GemvArgs& a, hipStream_t st, bool dry = false) {
-  // AIOS_GEMV_BF16_LDS=0: the round-1 persistent register GEMV instead (A/B runs)
-  static const bool on = !(std::getenv("AIOS_GEMV_BF16_LDS") && std::atoi(std::getenv("AIOS_GEMV_BF16_LDS")) == 0);
-  if (!on || a.B < 1 || a.B > 4 || a.K % 512 || a.N % 2 || a.epi == EPI_TP_RESID || a.tune_dbg ||
-      (a.kernel_sel != 0 && a.kernel_sel != 3))
-    return false;
-  for (int s = 0; s < a.nseg; ++s)
-    if (a.seg[s].qtype != QT_BF16 || a.seg[s].cols != a.K || (s > 0 && a.seg_row0[s] % 2)) return false;
-  const int npairs = a.N / 2;
-  const int G = std::min(a.tune_grid > 0 ? a.tune_grid : device_cu_count(), npairs);
-  const CuPlan pl{G, npairs, (2 * ((npairs + G - 1) / G) + 3) & ~3};
-  constexpr size_t LDS_MAX = 160 * 1024;
-  // R = 3 (two 28 KB slots in flight per CU, the quantised engine's batch-1 depth), R = 2 where the
-  // staged x rows leave no room (long K at B = 3..4)
-  // AIOS_LB_CFG (batch 1 only): slot geometry x ring depth -- 23 = 28 KB slots x 3 (default),
-  // 24 = 28 KB x 4, 14 = 14 KB x 4, 16 = 14 KB x 6 (profiles/decode_tinyllama_bf16_rocprof_r6.txt)
-  static const int cfg = [] {
-    const char* e = std::getenv("AIOS_LB_CFG");
-    return e ? std::atoi(e) : 23;
-  }();
-  if (a.B == 1 && cfg != 23) {
-    auto b1 = [&](auto gp, auto rr) -> bool {
-      constexpr int GP = decltype(gp)::value, RR = decltype(rr)::value;
-      const size_t lds = lb_lds_bytes<1, RR, GP>(a, pl);
-      if (lds > LDS_MAX) return false;
-      if (!dry) hipLaunchKernelGGL((gemv_lds16<1, RR, GP>), dim3(G), dim3(LG_THREADS), lds, st, a, pl);
-      return true;
-    };
-    using I = std::integral_constant<int, 1>;
-    using II = std::integral_constant<int, 2>;
-    if (cfg == 24 && b1(II{}, std::integral_constant<int, 4>{})) return true;
-    if (cfg == 14 && b1(I{}, std::integral_constant<int, 4>{})) return true;
-    if (cfg == 16 && b1(I{}, std::integral_constant<int, 6>{})) return true;
+inline void launch_gemv_lds16(const GemvArgs& a, const GemvPlan& p, hipStream_t st) {
+  static_assert(LbSlot<2>::BYTES == 14 * 2 * 1024 && LbSlot<1>::BYTES == 14 * 1024, "gemv_plan.h: BF16 engine slots");
+#define LB_CASE(B, R, GPW) \
+  case B * 100 + R * 10 + GPW: \
+    hipLaunchKernelGGL((gemv_lds16<B, R, GPW>), dim3(p.grid), dim3(p.threads), p.lds, st, a, p.cu); \
+    break
+  switch (p.B * 100 + p.R * 10 + p.GPW) {
+    LB_CASE(1, 4, 2);  // GemvKnobs::lb_cfg 24, 14, 16
+    LB_CASE(1, 4, 1);
+    LB_CASE(1, 6, 1);
+    LB_CASE(1, 3, 2);
+    LB_CASE(1, 2, 2);
+    LB_CASE(2, 3, 2);
+    LB_CASE(2, 2, 2);
+    LB_CASE(3, 3, 2);
+    LB_CASE(3, 2, 2);
+    LB_CASE(4, 3, 2);
+    LB_CASE(4, 2, 2);
+    default: throw std::runtime_error("gemv: no BF16 engine instantiation for the plan");
   }
-  auto go = [&](auto bt) -> bool {
-    constexpr int BB = decltype(bt)::value;
-    size_t lds = lb_lds_bytes<BB, 3>(a, pl);
-    if (lds <= LDS_MAX) {
-      if (!dry) hipLaunchKernelGGL((gemv_lds16<BB, 3>), dim3(G), dim3(LG_THREADS), lds, st, a, pl);
-      return true;
-    }
-    lds = lb_lds_bytes<BB, 2>(a, pl);
-    if (lds > LDS_MAX) return false;
-    if (!dry) hipLaunchKernelGGL((gemv_lds16<BB, 2>), dim3(G), dim3(LG_THREADS), lds, st, a, pl);
-    return true;
-  };
-  switch (a.B) {
-    case 1: return go(std::integral_constant<int, 1>{});
-    case 2: return go(std::integral_constant<int, 2>{});
-    case 3: return go(std::integral_constant<int, 3>{});
-    default: return go(std::integral_constant<int, 4>{});
-  }
+#undef LB_CASE
 }

@@ -898,141 +898,30 @@ __global__ void __launch_bounds__((q8_max_threads<U, PIPE>())) gemv_q8_rows(Gemv
   stamp(5);
 }
 
-template <int QT0, int QT1, int B>
-inline size_t q8_lds_bytes(int K) {
-  constexpr int W = QFmt<QT0>::W, R = QFmt<QT0>::RUNS;
-  return 64 * 4 + (size_t)B * (K / W) * R * 8 + (size_t)B * K + 2048 + 16;
-}
-
-// false (nothing launched): an EPI_TP_RESID launch whose rows do not fit the fused stage within the
-// co-residency cap -- the caller takes the separate all-reduce instead
-template <int QT0, int QT1, int B, int U, int PIPE>
-bool launch_q8_rows(const GemvArgs& a, size_t lds, hipStream_t st) {
-  static int occ = -1;
-  if (occ < 0) {
-    int o = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, gemv_q8_rows<QT0, QT1, B, U, PIPE>, Q8_WAVES * 64, lds) !=
-            hipSuccess || o <= 0)
-      o = 1;
-    occ = o;
+// the compiled instantiation of a q8 plan (GemvPlan::B, U, PIPE), handed to f as a GemvKernel tag
+template <int QT0, int QT1, class F>
+auto q8_visit(const GemvPlan& p, F&& f) {
+#define Q8_CASE(B, U, PIPE) \
+  case B * 100 + U * 10 + PIPE: return f(GemvKernel<gemv_q8_rows<QT0, QT1, B, U, PIPE>>{})
+  switch (p.B * 100 + p.U * 10 + p.PIPE) {
+    Q8_CASE(1, 1, 1);
+    Q8_CASE(1, 2, 1);
+    Q8_CASE(1, 3, 2);
+    Q8_CASE(1, 4, 2);
+    Q8_CASE(1, 1, 3);
+    Q8_CASE(1, 2, 3);
+    Q8_CASE(1, 1, 4);
+    Q8_CASE(1, 1, 2);
+    Q8_CASE(1, 2, 2);
+    Q8_CASE(1, 3, 1);
+    Q8_CASE(1, 4, 1);
+    Q8_CASE(1, 5, 1);
+    Q8_CASE(1, 6, 1);
+    Q8_CASE(1, 7, 1);
+    Q8_CASE(1, 8, 1);
+    Q8_CASE(2, 2, 2);
+    Q8_CASE(4, 2, 2);
+    default: return f(GemvKernel<gemv_q8_rows<QT0, QT1, 8, 1, 2>>{});
   }
-  int per_cu = std::min(occ, 2);
-  if (a.tune_grid > 0) per_cu = a.tune_grid;
-  const int npairs = a.N / 2;
-  const int cus = device_cu_count();
-  // Batch 1, one pair per wave: 8-wave workgroups leave CUs unequal whenever npairs / 8 is not a
-  // multiple of the CU count (Mistral QKV: 3072 pairs = 384 workgroups on 256 CUs -> half the CUs
-  // stream 16 pairs, half 8).  Instead size the workgroup to ceil(npairs / CUs) waves (<= 16) and
-  // launch one per CU: every CU streams the same bytes (AIOS_Q8_BALANCE=0: the 8-wave grid).
-  static const int balance = [] {
-    const char* e = std::getenv("AIOS_Q8_BALANCE");
-    return e ? std::atoi(e) : 1;
-  }();
-  int nw = Q8_WAVES;
-  int blocks = 0;
-  if (B == 1 && balance && a.tune_grid <= 0 && npairs >= 2 * cus) {
-    // round 4: also for the register-heavy U >= 3 variants (<= 8 waves) and for shapes with more
-    // pairs than waves (ppw pairs per wave, one workgroup per CU): TinyLlama's down (1024 pairs,
-    // U = 3) ran 128 8-wave workgroups on half the chip, its gate/up (5632 pairs) 512 workgroups with
-    // 1 or 2 pairs per wave
-    const int maxw = q8_max_threads<U, PIPE>() / 64;
-    const int ppw = (npairs + cus * maxw - 1) / (cus * maxw);
-    int want = (npairs + cus * ppw - 1) / (cus * ppw);
-    bool mixed = false;
-    int np0 = 0;
-    if (QT0 != QT1 && a.nseg > 1 && ppw == 1) {
-      // mixed formats: whole waves per format in every workgroup (the kernel splits nw by pair
-      // counts), e.g. TinyLlama's QKV 1152 Q4_K + 128 Q6_K pairs -> 5 + 1 waves, not 4 + 1
-      np0 = a.seg_row0[a.nseg - 1] / 2;
-      want = (np0 + cus - 1) / cus + (npairs - np0 + cus - 1) / cus;
-      mixed = true;
-    }
-    // several pairs per wave only for the long-K (U >= 3) shapes: TinyLlama's 5632-pair gate/up at
-    // U = 1 went 6.96 -> 9.15 us as 3 pairs per wave on one 8-wave workgroup per CU
-    // (profiles/decode_tinyllama_rocprof_r4.txt)
-    if (want >= 2 && want <= maxw && (ppw == 1 || U >= 3)) {
-      nw = want;
-      blocks = std::min(cus, (npairs + nw - 1) / nw);
-      if (mixed) {
-        // the grid must cover each format's pairs with ITS waves (the kernel's split below):
-        // 214 blocks x 5 Q4_K waves left 82 of TinyLlama's 1152 Q|K pairs to a second pass (9.5 us)
-        int nw0 = (int)(((long)nw * np0 + npairs / 2) / npairs);
-        nw0 = std::max(1, std::min(nw - 1, nw0));
-        const int nw1 = nw - nw0;
-        blocks = std::min(cus, std::max((np0 + nw0 - 1) / nw0, (npairs - np0 + nw1 - 1) / nw1));
-      }
-    }
-  }
-  if (!blocks) blocks = std::min((npairs + nw - 1) / nw, cus * per_cu);
-  if (a.epi == EPI_TP_RESID) {
-    // fused all-reduce: at most grid_cap workgroups (every rank sharing a GPU resident at once --
-    // spinning workgroups past it could wait on peers that cannot be scheduled), at most
-    // TPF_SLOTS, and each workgroup's pairs inside its stage slot (TPF_CAP values)
-    const int cap = a.grid_cap > 0 ? std::min(a.grid_cap, TPF_SLOTS) : TPF_SLOTS;
-    blocks = std::min(blocks, cap);
-    auto per_wg = [&](int g) { return 2 * nw * ((npairs + g * nw - 1) / (g * nw)); };
-    while (per_wg(blocks) > TPF_CAP && blocks < cap) ++blocks;
-    if (per_wg(blocks) > TPF_CAP) return false;
-    if (a.dry) return true;  // (TP init: every rank's fit for this shape is all-gathered first)
-  }
-  hipLaunchKernelGGL((gemv_q8_rows<QT0, QT1, B, U, PIPE>), dim3(blocks), dim3(nw * 64), lds, st, a);
-  return true;
-}
-
-template <int QT0, int QT1, int B>
-bool launch_gemv_q8(GemvArgs a, hipStream_t st) {
-  if constexpr (!same_xlayout<QT0, QT1>) {
-    return false;
-  } else {
-    const size_t lds = q8_lds_bytes<QT0, QT1, B>(a.K);
-    if (lds > 128 * 1024) return false;
-    a.kt_max = a.K;
-    if constexpr (B == 1) {
-      const int nch = a.K / QFmt<QT0>::W;
-      int u = a.tune_u;
-      if (u <= 0 || (u > 8 && u != 11 && u != 12 && u != 13 && u != 14 && u != 21 && u != 22 && u != 31)) {
-        // MI355X sweep (tools/gemv_probe.py --sweep): one chunk per lane per item for short K,
-        // except the mid-sized Q4_K/Q5_K projections; the whole K slice in flight for long K
-        // (U = 1 for the small/huge-N shapes won in the eager sweep but lost 2-3 % inside the
-        // captured decode step, so the whole-K-slice rule stays)
-        // (re-swept in the captured step, tools/gemv_knob_sweep.sh: U = 1 for K = 4096 gate/up
-        // +1.8 %, QKV +1 %, O / lm_head neutral)
-        u = nch <= 128 ? 1 : (nch <= 512 ? (nch + 63) / 64 : 2);
-        // Round 4 (tools/gemv_cu_probe.py row-kernel stamps): when the balanced launch gives every
-        // wave exactly ONE row pair, the double-buffered U = 1 pipeline issued the pair's second K
-        // half only after the x-staging barrier -- a second memory round trip on the critical path
-        // (O: barrier 1.9 us, pair computed 3.6 us).  The pair's whole K slice in one single-buffered
-        // item instead: QKV 8.27 -> 7.36 us, O 5.71 -> 5.05 (profiles/qkv_prologue_r4.txt).
-        const int npairs = a.N / 2;
-        static const int balance = [] {
-          const char* e = std::getenv("AIOS_Q8_BALANCE");
-          return e ? std::atoi(e) : 1;
-        }();
-        if (balance && a.tune_grid <= 0 && npairs <= 16 * device_cu_count() && nch <= 128)
-          u = nch <= 64 ? 11 : 12;
-      }
-      switch (u) {
-        case 11: return launch_q8_rows<QT0, QT1, 1, 1, 1>(a, lds, st);  // one pair per wave: the K slice in
-        case 12: return launch_q8_rows<QT0, QT1, 1, 2, 1>(a, lds, st);  // one single-buffered item
-        case 13: return launch_q8_rows<QT0, QT1, 1, 3, 2>(a, lds, st);  // tuning: U = 3/4 double-buffered
-        case 14: return launch_q8_rows<QT0, QT1, 1, 4, 2>(a, lds, st);
-        case 21: return launch_q8_rows<QT0, QT1, 1, 1, 3>(a, lds, st);  // tuning: triple / quad buffers
-        case 22: return launch_q8_rows<QT0, QT1, 1, 2, 3>(a, lds, st);
-        case 31: return launch_q8_rows<QT0, QT1, 1, 1, 4>(a, lds, st);
-        case 1: return launch_q8_rows<QT0, QT1, 1, 1, 2>(a, lds, st);
-        case 2: return launch_q8_rows<QT0, QT1, 1, 2, 2>(a, lds, st);
-        case 3: return launch_q8_rows<QT0, QT1, 1, 3, 1>(a, lds, st);
-        case 4: return launch_q8_rows<QT0, QT1, 1, 4, 1>(a, lds, st);
-        case 5: return launch_q8_rows<QT0, QT1, 1, 5, 1>(a, lds, st);
-        case 6: return launch_q8_rows<QT0, QT1, 1, 6, 1>(a, lds, st);
-        case 7: return launch_q8_rows<QT0, QT1, 1, 7, 1>(a, lds, st);
-        default: return launch_q8_rows<QT0, QT1, 1, 8, 1>(a, lds, st);
-      }
-    } else if constexpr (B == 8) {
-      return launch_q8_rows<QT0, QT1, 8, 1, 2>(a, lds, st);
-    } else {
-      return launch_q8_rows<QT0, QT1, B, 2, 2>(a, lds, st);
-    }
-    return true;
-  }
+#undef Q8_CASE
 }
