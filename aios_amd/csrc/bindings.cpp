@@ -55,6 +55,12 @@ GemmWs& gemm_ws(int M, int N) {
   return g;
 }
 
+struct PyQMatrix;
+// GemmQArgs from the arguments gemm_q / gemm_route / gemm_skinny_ntile share; kw: every other field by
+// name (device pointers as integers), an unknown name throws
+void gemm_q_args(GemmQArgs& a, const std::vector<PyQMatrix*>& segs, int lda, int M, int ldc, int epi, int ksplit,
+                 const py::kwargs& kw);
+
 // Owning device matrix in the repacked layout (tests / tools)
 struct PyQMatrix {
   QWeight w{};
@@ -104,6 +110,39 @@ struct PyQMatrix {
     if (buf) hipFree(buf);
   }
 };
+
+void gemm_q_args(GemmQArgs& a, const std::vector<PyQMatrix*>& segs, int lda, int M, int ldc, int epi, int ksplit,
+                 const py::kwargs& kw) {
+  std::memset(&a, 0, sizeof(a));
+  if (segs.empty() || segs.size() > 3) throw std::runtime_error("gemm_q: 1..3 segments");
+  a.lda = lda; a.nseg = (int)segs.size();
+  int n0 = 0;
+  for (int s = 0; s < a.nseg; ++s) { a.seg[s] = segs[s]->w; a.seg_n0[s] = n0; n0 += segs[s]->w.rows; }
+  a.M = M; a.N = n0; a.K = segs[0]->w.cols; a.ldc = ldc; a.epi = epi; a.ksplit = ksplit;
+  a.kv_inv_k = a.kv_inv_v = 1.f;
+  for (auto kv : kw) {
+    const std::string k = py::cast<std::string>(kv.first);
+    auto ptr = [&]() { return py::cast<uintptr_t>(kv.second); };
+    int* fi = k == "col0" ? &a.col0 : k == "head_dim" ? &a.head_dim : k == "q_dim" ? &a.q_dim : k == "kv_dim" ? &a.kv_dim
+            : k == "n_kv_heads" ? &a.n_kv_heads : k == "max_ctx" ? &a.max_ctx : k == "kv_fp8" ? &a.kv_fp8
+            : k == "nrm_parts" ? &a.nrm_parts : nullptr;
+    float* ff = k == "kv_inv_k" ? &a.kv_inv_k : k == "kv_inv_v" ? &a.kv_inv_v : k == "nrm_eps" ? &a.nrm_eps : nullptr;
+    if (fi) *fi = py::cast<int>(kv.second);
+    else if (ff) *ff = py::cast<float>(kv.second);
+    else if (k == "rope_cs") a.rope_cs = (const float2*)ptr();
+    else if (k == "pos") a.pos = (const int*)ptr();
+    else if (k == "slot") a.slot = (const int*)ptr();
+    else if (k == "block_table") a.block_table = (const int*)ptr();
+    else if (k == "q_out") a.q_out = (float*)ptr();
+    else if (k == "k_cache") a.k_cache = (bf16_t*)ptr();
+    else if (k == "v_cache") a.v_cache = (bf16_t*)ptr();
+    else if (k == "nrm_g") a.nrm_g = (const float*)ptr();
+    else if (k == "nrm_out16") a.nrm_out16 = (bf16_t*)ptr();
+    else if (k == "nrm_part") a.nrm_part = (float*)ptr();
+    else if (k == "nrm_in") a.nrm_in = (const float*)ptr();
+    else throw std::runtime_error("gemm_q: unknown argument " + k);
+  }
+}
 
 }  // namespace
 
@@ -395,6 +434,17 @@ PYBIND11_MODULE(_engine, m) {
       .def("get_rows", [](PyQMatrix& q, uintptr_t rows, int n, uintptr_t out, int ldo, uintptr_t st) {
         launch_get_rows(q.w, (const int*)rows, n, (float*)out, ldo, 1.f, S(st));
       })
+      // get_rows + the per-step lookups of the batch-1 QKV epilogue (StepPrep, ops.h)
+      .def("get_rows_step",
+           [](PyQMatrix& q, uintptr_t rows, int n, uintptr_t out, int ldo, uintptr_t st, uintptr_t pos, uintptr_t slot,
+              uintptr_t block_table, int maxb, uintptr_t rope_cs, int half, uintptr_t kv, uintptr_t rope) {
+             const StepPrep sp{(const int*)pos, (const int*)slot, (const int*)block_table, maxb, (const float2*)rope_cs,
+                               half, (int*)kv, (float2*)rope};
+             launch_get_rows_step(q.w, (const int*)rows, n, (float*)out, ldo, 1.f, sp, S(st));
+           },
+           py::arg("rows"), py::arg("n"), py::arg("out"), py::arg("ldo"), py::arg("st"), py::arg("pos"),
+           py::arg("slot") = 0, py::arg("block_table") = 0, py::arg("maxb") = 0, py::arg("rope_cs") = 0,
+           py::arg("half") = 0, py::arg("kv") = 0, py::arg("rope") = 0)
       .def("fill_random", [](PyQMatrix& q, uint64_t seed, float amp) {
         fill_random_weight(q.w, seed, amp, nullptr);
         HIP_CHECK(hipDeviceSynchronize());
@@ -594,19 +644,23 @@ PYBIND11_MODULE(_engine, m) {
   m.def("qkv_post",
         [](uintptr_t qkv, int ldqkv, int T, int H, int Hkv, int hd, uintptr_t q_norm, uintptr_t k_norm, float eps,
            int rope_neox, float rope_base, uintptr_t pos, uintptr_t slot, uintptr_t q_out, uintptr_t k_cache,
-           uintptr_t v_cache, int max_ctx, uintptr_t st, uintptr_t block_table) {
+           uintptr_t v_cache, int max_ctx, uintptr_t st, uintptr_t block_table, uintptr_t rope_cs, uintptr_t bias,
+           int kv_fp8, float kv_inv_k, float kv_inv_v, uintptr_t amax) {
           QkvPostArgs a;
+          a.bias = (const float*)bias; a.kv_fp8 = kv_fp8; a.kv_inv_k = kv_inv_k; a.kv_inv_v = kv_inv_v;
+          a.amax = (unsigned*)amax;
           a.block_table = (const int*)block_table;
           a.qkv = (const float*)qkv; a.ldqkv = ldqkv; a.T = T; a.n_heads = H; a.n_kv_heads = Hkv; a.head_dim = hd;
           a.q_norm = (const float*)q_norm; a.k_norm = (const float*)k_norm; a.eps = eps; a.rope_neox = rope_neox;
-          a.rope_base = rope_base; a.rope_cs = nullptr; a.pos = (const int*)pos; a.slot = (const int*)slot; a.q_out = (float*)q_out;
+          a.rope_base = rope_base; a.rope_cs = (const float2*)rope_cs; a.pos = (const int*)pos; a.slot = (const int*)slot; a.q_out = (float*)q_out;
           a.k_cache = (bf16_t*)k_cache; a.v_cache = (bf16_t*)v_cache; a.max_ctx = max_ctx;
           launch_qkv_post(a, S(st));
         },
         py::arg("qkv"), py::arg("ldqkv"), py::arg("T"), py::arg("H"), py::arg("Hkv"), py::arg("hd"), py::arg("q_norm"),
         py::arg("k_norm"), py::arg("eps"), py::arg("rope_neox"), py::arg("rope_base"), py::arg("pos"), py::arg("slot"),
         py::arg("q_out"), py::arg("k_cache"), py::arg("v_cache"), py::arg("max_ctx"), py::arg("st"),
-        py::arg("block_table") = 0);
+        py::arg("block_table") = 0, py::arg("rope_cs") = 0, py::arg("bias") = 0, py::arg("kv_fp8") = 0,
+        py::arg("kv_inv_k") = 1.f, py::arg("kv_inv_v") = 1.f, py::arg("amax") = 0);
   // host side of the fp8 KV calibration: observed table -> per-layer (K, V) scales
   m.def("kv_scales_from_amax", &kv_scales_from_amax, py::arg("amax"), py::arg("n_layers"), py::arg("n_kv_heads"),
         py::arg("headroom") = 2.f);
@@ -660,16 +714,15 @@ PYBIND11_MODULE(_engine, m) {
   m.def("gemm_supports", &gemm_supports);
   m.def(
       "gemm_q",
+      // kw: the GemmQArgs fields of the fused epilogues, each defaulting to 0 / null (kv_inv_* to 1) --
+      // GEPI_QKV: col0, head_dim, q_dim, kv_dim, n_kv_heads, max_ctx, rope_cs, pos, slot, block_table,
+      // q_out, k_cache, v_cache, kv_fp8, kv_inv_k, kv_inv_v; the split RMSNorm: nrm_g, nrm_out16,
+      // nrm_part, nrm_in, nrm_parts, nrm_eps
       [](uintptr_t A, int lda, std::vector<PyQMatrix*> segs, int M, uintptr_t C, uintptr_t C16, int ldc, int epi,
-         uintptr_t st, int ksplit, uintptr_t dbg_ts) {
+         uintptr_t st, int ksplit, uintptr_t dbg_ts, py::kwargs kw) {
         GemmQArgs a;
-        std::memset(&a, 0, sizeof(a));
-        if (segs.empty() || segs.size() > 3) throw std::runtime_error("gemm_q: 1..3 segments");
-        a.A = (const bf16_t*)A; a.lda = lda; a.nseg = (int)segs.size();
-        int n0 = 0;
-        for (int s = 0; s < a.nseg; ++s) { a.seg[s] = segs[s]->w; a.seg_n0[s] = n0; n0 += segs[s]->w.rows; }
-        a.M = M; a.N = n0; a.K = segs[0]->w.cols;
-        a.C = (float*)C; a.C16 = (bf16_t*)C16; a.ldc = ldc; a.epi = epi; a.ksplit = ksplit;
+        gemm_q_args(a, segs, lda, M, ldc, epi, ksplit, kw);
+        a.A = (const bf16_t*)A; a.C = (float*)C; a.C16 = (bf16_t*)C16;
         a.dbg_ts = (unsigned long long*)dbg_ts;
         GemmWs& g = gemm_ws(M, a.N);
         a.ws = g.ws; a.ws_bytes = g.bytes; a.cnt = g.cnt; a.cnt_len = g.cnt_len;
@@ -677,6 +730,45 @@ PYBIND11_MODULE(_engine, m) {
       },
       py::arg("A"), py::arg("lda"), py::arg("segs"), py::arg("M"), py::arg("C"), py::arg("C16"), py::arg("ldc"),
       py::arg("epi"), py::arg("stream"), py::arg("ksplit") = 0, py::arg("dbg_ts") = 0);
+  // which kernel launch_gemm_q would hand each format-split launch of the same call to (no launch):
+  // [(col0, "ring" | "pf" | "skinny" | "big")].  gemm_q's arguments minus the buffers: A, C / C16 count
+  // as present and aligned; the keyword pointers are only tested for null, pass what gemm_q gets
+  m.def(
+      "gemm_route",
+      [](int lda, std::vector<PyQMatrix*> segs, int M, int ldc, int epi, int ksplit, py::kwargs kw) {
+        GemmQArgs a;
+        gemm_q_args(a, segs, lda, M, ldc, epi, ksplit, kw);
+        a.A = (const bf16_t*)(uintptr_t)256;
+        if (epi == GEPI_SWIGLU_BF16) a.C16 = (bf16_t*)(uintptr_t)256;
+        else a.C = (float*)(uintptr_t)256;
+        GemmWs& g = gemm_ws(M, a.N);  // (the split-K workspace gemm_q would pass)
+        a.ws = g.ws; a.ws_bytes = g.bytes; a.cnt = g.cnt; a.cnt_len = g.cnt_len;
+        static const char* names[] = {"ring", "pf", "skinny", "big"};
+        py::list out;
+        for (const GemmRoute& r : gemm_route(a)) out.append(py::make_tuple(r.col0, names[r.kernel]));
+        return out;
+      },
+      py::arg("lda"), py::arg("segs"), py::arg("M"), py::arg("ldc"), py::arg("epi"), py::arg("ksplit") = 0);
+  // output tiles of the skinny kernel for a stack at M rows (AIOS_SKINNY_RB is read per call): the
+  // nrm_parts of a GEPI_ACCUM_NORM producer, as the engine sizes it
+  m.def(
+      "gemm_skinny_ntile",
+      [](std::vector<PyQMatrix*> segs, int M) {
+        GemmQArgs a;
+        gemm_q_args(a, segs, segs.empty() ? 0 : segs[0]->w.cols, M, 0, GEPI_STORE, 0, py::kwargs());
+        return gemm_skinny_ntile(a);
+      },
+      py::arg("segs"), py::arg("M"));
+  // residual[m][:] += data[m][:] (data 0: residual holds the sum) + the split-RMSNorm producer outputs
+  m.def(
+      "add_norm",
+      [](uintptr_t residual, uintptr_t data, int rows, int d, uintptr_t g, uintptr_t out16, int ld16, uintptr_t part,
+         int parts, uintptr_t st) {
+        launch_add_norm((float*)residual, (const float*)data, rows, d,
+                        ResidNorm{(const float*)g, (bf16_t*)out16, ld16, (float*)part, parts}, S(st));
+      },
+      py::arg("residual"), py::arg("data"), py::arg("rows"), py::arg("d"), py::arg("g"), py::arg("out16"),
+      py::arg("ld16"), py::arg("part"), py::arg("parts"), py::arg("st") = 0);
   m.def(
       "gemm_pf_plan",
       [](std::vector<PyQMatrix*> segs, int M, int epi, int ksplit) {
@@ -704,6 +796,8 @@ PYBIND11_MODULE(_engine, m) {
   m.attr("GEPI_STORE") = (int)GEPI_STORE;
   m.attr("GEPI_ACCUM") = (int)GEPI_ACCUM;
   m.attr("GEPI_SWIGLU_BF16") = (int)GEPI_SWIGLU_BF16;
+  m.attr("GEPI_QKV") = (int)GEPI_QKV;
+  m.attr("GEPI_ACCUM_NORM") = (int)GEPI_ACCUM_NORM;
   m.def(
       "attn_prefill",
       [](uintptr_t q, uintptr_t k, uintptr_t v, int slot, int start, int T, int H, int Hkv, int hd, int max_ctx,

@@ -230,19 +230,30 @@ static void launch_big(const GemmQArgs& a, hipStream_t st) {
 
 // M <= 64: the skinny kernel (gemm_skinny.hip) streams the quantised weights straight into MFMA
 // operand registers; returns false when the shape / workspace does not fit it
-bool launch_gemm_skinny(const GemmQArgs& a, hipStream_t st);
+bool launch_gemm_skinny(const GemmQArgs& a, hipStream_t st);  // (asks gemm_skinny_serves first)
 bool gemm_skinny_mixed_ok(const GemmQArgs& a);
 // M <= 32, Q4_K / Q6_K: the LDS-DMA ring GEMM (gemm_ring.hip); false when it does not serve the shape
 bool launch_gemm_ring(const GemmQArgs& a, hipStream_t st);
 // M >= 33, Q4_K / Q6_K / mixed / bf16 stacks: the LDS-DMA prefill GEMM (gemm_pf.hip)
 bool launch_gemm_pf(const GemmQArgs& a, hipStream_t st);
 
-static void launch_one(const GemmQArgs& a, hipStream_t st) {
+// the kernel of one single-format launch (launch_one runs it, gemm_route reports it)
+static int pick_one(const GemmQArgs& a) {
   static const int skinny_max = env_int("AIOS_GEMM_SKINNY_MAX_M", 64);
-  if (launch_gemm_ring(a, st)) return;
-  if (a.M <= skinny_max && launch_gemm_skinny(a, st)) return;
+  if (gemm_ring_serves(a)) return GK_RING;
+  if (a.M <= skinny_max && gemm_skinny_serves(a)) return GK_SKINNY;
   if (a.epi == GEPI_QKV || a.epi == GEPI_ACCUM_NORM || a.nrm_in)
     throw std::runtime_error("gemm: the QKV / fused-RMSNorm epilogues need the skinny (M <= 64) kernel");
+  return GK_BIG;
+}
+
+static void launch_one(const GemmQArgs& a, hipStream_t st) {
+  const int k = pick_one(a);
+  if (k == GK_RING || k == GK_SKINNY) {
+    if (!(k == GK_RING ? launch_gemm_ring(a, st) : launch_gemm_skinny(a, st)))
+      throw std::logic_error("gemm: a kernel declined a launch its predicate accepted");
+    return;
+  }
   switch (a.seg[0].qtype) {
     case QT_Q4_K: launch_big<QT_Q4_K>(a, st); break;
     case QT_Q5_K: launch_big<QT_Q5_K>(a, st); break;
@@ -255,9 +266,7 @@ static void launch_one(const GemmQArgs& a, hipStream_t st) {
   }
 }
 
-// Segments sharing a format go in one launch; a format change starts a new launch whose C
-// pointer is shifted to the segment's first column (e.g. Q4_K Q/K + Q6_K V in Q4_K_M layers).
-void launch_gemm_q(const GemmQArgs& a, hipStream_t st) {
+static void gemm_q_check(const GemmQArgs& a) {
   if (a.K % 64) throw std::runtime_error("gemm: K must be a multiple of 64");
   if (a.nseg < 1 || a.nseg > 3) throw std::runtime_error("gemm: 1..3 weight segments");
   if (a.M < 1) return;
@@ -267,11 +276,12 @@ void launch_gemm_q(const GemmQArgs& a, hipStream_t st) {
     if (a.seg[s].rows % 64 || a.seg_n0[s] % 64) throw std::runtime_error("gemm: segment sizes must be multiples of 64");
   }
   if (a.N % 64) throw std::runtime_error("gemm: N must be a multiple of 64");
-  // mixed formats in ONE skinny launch where supported (the Q4_K_M QKV stack)
-  static const int skinny_max = env_int("AIOS_GEMM_SKINNY_MAX_M", 64);
-  if (launch_gemm_ring(a, st)) return;  // the mixed Q4_K_M QKV stack in one ring launch
-  if (launch_gemm_pf(a, st)) return;    // prefill chunks: the mixed stack in one launch too
-  if (a.M <= skinny_max && gemm_skinny_mixed_ok(a) && launch_gemm_skinny(a, st)) return;
+}
+
+// Segments sharing a format go in one launch; a format change starts a new launch whose C
+// pointer is shifted to the segment's first column (e.g. Q4_K Q/K + Q6_K V in Q4_K_M layers).
+template <class F>
+static void gemm_q_split(const GemmQArgs& a, F&& fn) {
   int s0 = 0;
   while (s0 < a.nseg) {
     int s1 = s0 + 1;
@@ -291,9 +301,33 @@ void launch_gemm_q(const GemmQArgs& a, hipStream_t st) {
     } else {
       b.C = a.C + c0;
     }
-    launch_one(b, st);
+    fn(b);
     s0 = s1;
   }
+}
+
+void launch_gemm_q(const GemmQArgs& a, hipStream_t st) {
+  gemm_q_check(a);
+  if (a.M < 1) return;
+  // mixed formats in ONE skinny launch where supported (the Q4_K_M QKV stack)
+  static const int skinny_max = env_int("AIOS_GEMM_SKINNY_MAX_M", 64);
+  if (launch_gemm_ring(a, st)) return;  // the mixed Q4_K_M QKV stack in one ring launch
+  if (launch_gemm_pf(a, st)) return;    // prefill chunks: the mixed stack in one launch too
+  if (a.M <= skinny_max && gemm_skinny_mixed_ok(a) && launch_gemm_skinny(a, st)) return;
+  gemm_q_split(a, [&](const GemmQArgs& b) { launch_one(b, st); });
+}
+
+// launch_gemm_q's decisions without the launches, from the launchers' own predicates
+std::vector<GemmRoute> gemm_route(const GemmQArgs& a) {
+  std::vector<GemmRoute> out;
+  gemm_q_check(a);
+  if (a.M < 1) return out;
+  static const int skinny_max = env_int("AIOS_GEMM_SKINNY_MAX_M", 64);
+  if (gemm_ring_serves(a)) return {{a.col0, GK_RING}};
+  if (gemm_pf_serves(a)) return {{a.col0, GK_PF}};
+  if (a.M <= skinny_max && gemm_skinny_mixed_ok(a) && gemm_skinny_serves(a)) return {{a.col0, GK_SKINNY}};
+  gemm_q_split(a, [&](const GemmQArgs& b) { out.push_back({b.col0, pick_one(b)}); });
+  return out;
 }
 
 // single-segment form kept for the bindings / tests

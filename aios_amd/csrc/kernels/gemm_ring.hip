@@ -350,8 +350,9 @@ static bool rg_launch(const GemmQArgs& a, hipStream_t st) {
 }
 
 // AIOS_GEMM_RING: 1 (default) = the ring GEMM serves the batched-decode shapes it supports
-// (M 5..32, Q4_K / Q6_K / mixed Q4_K|Q6_K, 128-row tiles, K % 256 == 0); 0 = skinny only
-bool launch_gemm_ring(const GemmQArgs& a, hipStream_t st) {
+// (M 5..32, Q4_K / Q6_K / mixed Q4_K|Q6_K, 128-row tiles, K % 256 == 0); 0 = skinny only.
+// gemm_ring_serves: whether launch_gemm_ring takes these args (the launcher asks it first; gemm_route)
+bool gemm_ring_serves(const GemmQArgs& a) {
   static const int on = rg_env("AIOS_GEMM_RING", 1);
   static const int min_m = rg_env("AIOS_GEMM_RING_MIN_M", 2);
   if (!on || a.M < min_m || a.M > 32 || a.N % 128 || a.K % 256 || a.lda % 8) return false;
@@ -365,6 +366,15 @@ bool launch_gemm_ring(const GemmQArgs& a, hipStream_t st) {
   const int qt0 = a.seg[0].qtype, qt1 = a.seg[a.nseg - 1].qtype;
   for (int s = 0; s + 1 < a.nseg; ++s)
     if (a.seg[s].qtype != qt0) return false;
+  // the instantiated format pairs (go() below)
+  if (qt0 == QT_Q4_K && qt1 == QT_Q4_K) return true;
+  if (qt0 == QT_Q6_K && qt1 == QT_Q6_K) return true;
+  return qt0 == QT_Q4_K && qt1 == QT_Q6_K && (a.epi == GEPI_QKV || a.epi == GEPI_STORE);
+}
+
+bool launch_gemm_ring(const GemmQArgs& a, hipStream_t st) {
+  if (!gemm_ring_serves(a)) return false;
+  const int qt0 = a.seg[0].qtype, qt1 = a.seg[a.nseg - 1].qtype;
   auto go = [&](auto mt, auto xr) {
     constexpr int MT = decltype(mt)::value;
     constexpr bool XR = decltype(xr)::value;

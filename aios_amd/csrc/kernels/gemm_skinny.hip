@@ -376,11 +376,19 @@ bool gemm_skinny_mixed_ok(const GemmQArgs& a) {
   return q1 == QT_Q6_K && (a.epi == GEPI_QKV || a.epi == GEPI_STORE);
 }
 
-bool launch_gemm_skinny(const GemmQArgs& a, hipStream_t st) {
+// whether launch_gemm_skinny takes these args (the launcher asks it first; gemm_route)
+bool gemm_skinny_serves(const GemmQArgs& a) {
   if (!sk_fits(a)) return false;
+  for (int s = 1; s < a.nseg; ++s)
+    if (a.seg[s].qtype != a.seg[0].qtype) return gemm_skinny_mixed_ok(a);
+  return true;  // (sk_fits checked the format)
+}
+
+bool launch_gemm_skinny(const GemmQArgs& a, hipStream_t st) {
+  if (!gemm_skinny_serves(a)) return false;
   bool same = true;
   for (int s = 1; s < a.nseg; ++s) same &= a.seg[s].qtype == a.seg[0].qtype;
-  if (!same) return gemm_skinny_mixed_ok(a) && sk_qt<QT_Q4_K, QT_Q6_K>(a, st);
+  if (!same) return sk_qt<QT_Q4_K, QT_Q6_K>(a, st);
   switch (a.seg[0].qtype) {
     case QT_Q4_K: return sk_qt<QT_Q4_K, QT_Q4_K>(a, st);
     case QT_Q5_K: return sk_qt<QT_Q5_K, QT_Q5_K>(a, st);

@@ -268,6 +268,18 @@ int gemm_skinny_cnt_len(int N);
 // output tiles of the skinny kernel for these args (0: not served by the skinny kernel)
 int gemm_skinny_ntile(const GemmQArgs& a);
 void launch_gemm_q(const GemmQArgs& a, hipStream_t st);
+// Which kernel launch_gemm_q hands each of its format-split launches to, without launching: one
+// entry per launch, col0 = the launch's first global column.  Asks the launchers' own predicates in
+// launch_gemm_q's order and throws where it would (bindings / tests: a test asserts the kernel it
+// means to exercise).
+enum GemmKernel { GK_RING = 0, GK_PF = 1, GK_SKINNY = 2, GK_BIG = 3 };
+struct GemmRoute {
+  int col0;
+  int kernel;
+};
+std::vector<GemmRoute> gemm_route(const GemmQArgs& a);
+bool gemm_ring_serves(const GemmQArgs& a);    // launch_gemm_ring would take a (gemm_ring.hip)
+bool gemm_skinny_serves(const GemmQArgs& a);  // launch_gemm_skinny would take a (gemm_skinny.hip)
 // the prefill GEMM (kernels/gemm_pf.hip): true if it took the launch; its tile / split plan for a shape
 bool launch_gemm_pf(const GemmQArgs& a, hipStream_t st);
 bool gemm_pf_serves(const GemmQArgs& a);  // launch_gemm_pf would take a (gemm_pf.hip)

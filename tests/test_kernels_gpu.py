@@ -613,6 +613,14 @@ def test_qkv_post_qknorm(E, neox):
     assert torch.allclose(q.cpu().view(T, H, hd), qr, atol=1e-4, rtol=1e-4)
     for t in range(T):
         assert torch.allclose(kc[0, :, int(pos[t])].float().cpu(), kr[t], atol=2e-2, rtol=1e-2)
+    # V: no norm, no RoPE -- the input rounded to bf16, bit for bit, at (head, pos[t]) and nowhere else
+    vc = unpaged(vp, 1, max_ctx).cpu()
+    vr = c[:, (H + Hkv) * hd:].view(T, Hkv, hd).to(torch.bfloat16)
+    for t in range(T):
+        assert torch.equal(vc[0, :, int(pos[t])].view(torch.int16), vr[t].view(torch.int16))
+    other = torch.ones(max_ctx, dtype=torch.bool)
+    other[pos.cpu().long()] = False
+    assert not vc[0][:, other].view(torch.int16).any()
 
 
 def test_sample_greedy_and_mask(E):
