@@ -514,9 +514,11 @@ PYBIND11_MODULE(_engine, m) {
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t seq_len, uintptr_t slot, int B, int H, int Hkv, int hd,
            int max_ctx, int n_chunks, float scale, uintptr_t opart, uintptr_t ml, uintptr_t out, uintptr_t counters,
            uintptr_t st, int split, uintptr_t block_table, int bt_rows, uintptr_t ts, int kv_fp8, float k_scale,
-           float v_scale) {
+           float v_scale, uintptr_t out16, int out_wt, int short_len, int kv_tail, int kv_nt, int combine_trips) {
           AttnDecodeArgs a;
           a.split = split;
+          a.out16 = (bf16_t*)out16; a.out_wt = out_wt; a.short_len = short_len; a.kv_tail = kv_tail; a.kv_nt = kv_nt;
+          a.combine_trips = combine_trips;
           a.kv_fp8 = kv_fp8; a.kv_scale_k = k_scale; a.kv_scale_v = v_scale;
           a.ts = (unsigned long long*)ts;
           a.block_table = (const int*)block_table; a.bt_rows = bt_rows;
@@ -531,7 +533,8 @@ PYBIND11_MODULE(_engine, m) {
         py::arg("Hkv"), py::arg("hd"), py::arg("max_ctx"), py::arg("n_chunks"), py::arg("scale"), py::arg("opart"),
         py::arg("ml"), py::arg("out"), py::arg("counters"), py::arg("st"), py::arg("split") = 0,
         py::arg("block_table") = 0, py::arg("bt_rows") = 0, py::arg("ts") = 0, py::arg("kv_fp8") = 0,
-        py::arg("k_scale") = 1.f, py::arg("v_scale") = 1.f);
+        py::arg("k_scale") = 1.f, py::arg("v_scale") = 1.f, py::arg("out16") = 0, py::arg("out_wt") = 0,
+        py::arg("short_len") = -1, py::arg("kv_tail") = -1, py::arg("kv_nt") = -1, py::arg("combine_trips") = 0);
   m.def("attn_decode_split", &attn_decode_split);
   // physical identity of a device (PCI bus id): ranks that share a GPU see the same string
   // the host-built launch descriptor of the one-workgroup-per-CU GEMVs (gemv_desc.h; no GPU needed):

@@ -145,7 +145,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
       r.v[i] = *(const PT*)(vc + off);
     });
   };
-  auto stage = [&](const Regs& r, bf16_t* buf) {
+  // LAST: the tile is the block's last one (or the odd count's pad tile, a re-read of it).  Its keys
+  // past last_pos are not written yet -- a recycled page may hold any bit pattern there, NaN and Inf
+  // included -- and their P^T = 0 does not cancel a non-finite V in the MFMA (0 x NaN), so their V rows
+  // are staged as zeros.  (K needs nothing: a masked score is overwritten with -inf.)
+  auto stage_tile = [&](const Regs& r, bf16_t* buf, auto LAST) {
+    const int dead0 = last_pos + 1 - nt_last * FP_KT;  // first dead key of the last tile
     bf16_t* sK = buf;
     bf16_t* sV = buf + FP_KT * KROW;
     static_for<PPT>([&](auto I) {
@@ -161,12 +166,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
           return o;
         };
         *(u32x4_t*)(sK + key * KROW + c * 8) = cv(r.k[i]);
-        *(u32x4_t*)(sV + key * VROW + c * 8) = cv(r.v[i]);
+        u32x4_t v = cv(r.v[i]);
+        if (decltype(LAST)::value && key >= dead0) v = u32x4_t{0, 0, 0, 0};
+        *(u32x4_t*)(sV + key * VROW + c * 8) = v;
       } else {
         *(u32x4_t*)(sK + key * KROW + c * 8) = r.k[i];
-        *(u32x4_t*)(sV + key * VROW + c * 8) = r.v[i];
+        u32x4_t v = r.v[i];
+        if (decltype(LAST)::value && key >= dead0) v = u32x4_t{0, 0, 0, 0};
+        *(u32x4_t*)(sV + key * VROW + c * 8) = v;
       }
     });
+  };
+  // (workgroup-uniform branch: the full tiles before the last one pay nothing else)
+  auto stage = [&](const Regs& r, bf16_t* buf, int kt) {
+    if (kt >= nt_last) stage_tile(r, buf, std::true_type{});
+    else stage_tile(r, buf, std::false_type{});
   };
   // one 64-key tile of math on LDS buffer buf (a tile past the last one -- the odd count's pad --
   // is fully masked: p = 0, alpha = 1)
@@ -259,16 +273,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   Regs A, B;
   load(A, 0);
   load(B, 1);
-  stage(A, L0);
+  stage(A, L0, 0);
   __syncthreads();
   for (int kt = 0; kt < ntiles; kt += 2) {
     load(A, kt + 2);
     math(L0, kt);
-    stage(B, L1);
+    stage(B, L1, kt + 1);
     __syncthreads();
     load(B, kt + 3);
     math(L1, kt + 1);
-    stage(A, L0);
+    stage(A, L0, kt + 2);
     __syncthreads();
   }
   // ---- normalise and store bf16: O^T[dim][row], dim = 32 i + (r&3) + 8 (r>>2) + 4 half

@@ -106,7 +106,8 @@ struct AttnDecodeArgs {
   const bf16_t* v_cache;
   const int* block_table = nullptr;  // [slots][max_ctx / KV_BLOCK] or null (identity)
   int bt_rows = 0;         // block_table indexed by row b instead of slot[b]
-  const int* seq_len;      // [B] number of valid keys (pos+1)
+  const int* seq_len;      // [B] number of valid keys (pos+1); >= 1 -- an empty row (0) is never passed: its
+                           // output is 0/0 (other rows and the counters are unaffected)
   const int* slot;         // [B] or null
   int B, n_heads, n_kv_heads, head_dim, max_ctx;
   int n_chunks;            // grid chunks (>= ceil(max_len / ATTN_CHUNK))
@@ -121,6 +122,7 @@ struct AttnDecodeArgs {
   unsigned long long* ts = nullptr;  // probes: [grid][8] s_memrealtime phase stamps (tools/attn_probe.py --stamps)
   int kv_nt = -1;          // long mode: K/V loads with the streaming (nt) policy (-1: AIOS_ATTN_NT, default 1)
   int kv_tail = -1;        // last partial block: loads only for live keys (-1: AIOS_ATTN_TAIL, default 1)
+                           // (0 requires finite dead keys: their V is loaded and multiplied by p = 0)
   int combine_trips = 0;   // split-K combine: 0 = launcher (AIOS_ATTN_COMBINE, default one round trip), 2 = two
   int out_wt = 0;          // fp32 out with write-through (agent-scope) stores
   int kv_fp8 = 0;          // fp8 e4m3 pool: value = code * kv_scale_{k,v}

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from aios_amd.gguf.quants import GGMLType, dequantize, quantize
+from attention_oracle import paged as paged_cache, unpaged  # noqa: F401  (one definition: the oracle's)
 
 pytestmark = pytest.mark.gpu
 
@@ -13,28 +14,6 @@ QTS = [GGMLType.Q4_K, GGMLType.Q6_K, GGMLType.Q5_K, GGMLType.Q4_0, GGMLType.Q8_0
 
 
 KVB = 128  # paged KV block (E.KV_BLOCK)
-
-
-def paged_cache(x, shuffle=False, seed=0):
-    """Logical KV [S, Hkv, C, hd] -> (physical pool [S*C/KVB, Hkv, KVB, hd], block table [S, C/KVB] or
-    None for the identity map).  shuffle scatters the logical blocks over a random permutation."""
-    S, Hk, C, D = x.shape
-    nb = C // KVB
-    blocks = x.reshape(S, Hk, nb, KVB, D).permute(0, 2, 1, 3, 4).reshape(S * nb, Hk, KVB, D)
-    if not shuffle:
-        return blocks.contiguous(), None
-    perm = torch.randperm(S * nb, generator=torch.Generator().manual_seed(seed))
-    phys = torch.empty_like(blocks)
-    phys[perm] = blocks
-    return phys.contiguous(), perm.view(S, nb).to(torch.int32)
-
-
-def unpaged(phys, S, C, bt=None):
-    """Inverse of paged_cache: physical pool (+ table) -> logical [S, Hkv, C, hd]."""
-    nb = C // KVB
-    blocks = phys if bt is None else phys[bt.reshape(-1).long().to(phys.device)]
-    Hk, D = phys.shape[1], phys.shape[3]
-    return blocks.reshape(S, nb, Hk, KVB, D).permute(0, 2, 1, 3, 4).reshape(S, Hk, C, D)
 
 
 @pytest.fixture(scope="module")
@@ -425,7 +404,8 @@ def test_gemv_b1_cu_qkv(E, mixed, table, grid, sel):
     assert int((kc != 0).sum()) == Hkv * hd and int((vc != 0).sum()) == Hkv * hd
 
 
-@pytest.mark.parametrize("hd,H,Hkv", [(64, 8, 1), (128, 32, 8), (64, 32, 4), (128, 40, 8)])
+@pytest.mark.parametrize("hd,H,Hkv", [(64, 8, 1), (128, 32, 8), (64, 32, 4), (128, 40, 8),
+                                       (64, 4, 4), (128, 12, 6)])  # (the last two: G = 1 and G = 2)
 @pytest.mark.parametrize("lens,max_ctx", [([1], 256), ([37, 200], 256), ([64, 65, 129, 1], 256),
                                           ([256, 255, 192], 256),
                                           # several 512-key splits: exercises the cross-workgroup combine
