@@ -381,7 +381,7 @@ constexpr int SAMPLE_THREADS = 256;
 constexpr int SAMPLE_PER_THREAD = 16;
 constexpr int SAMPLE_SLICE = SAMPLE_THREADS * SAMPLE_PER_THREAD;
 constexpr int SAMPLE_KCAP = 256;          // candidates per slice (top-k above 256 is clamped)
-constexpr int SAMPLE_MAX_CAND = 4096;     // candidates the merge holds (16 per thread)
+constexpr int SAMPLE_MAX_CAND = 4096;     // candidates the merge holds at a time (16 per thread); more: rounds
 constexpr int SAMPLE_TOPP_K = 256;        // candidate set of top-p when top-k is off
 
 static inline int sample_slices(int V) { return (V + SAMPLE_SLICE - 1) / SAMPLE_SLICE; }
@@ -416,9 +416,14 @@ __device__ __forceinline__ float gumbel(uint64_t seed, uint32_t step, int b, int
 // select on a 24-bit quantisation of (v - (hi - span)), 8 bits per pass (an LDS histogram of the digit under
 // the prefix found so far, a block suffix scan, the digit where the count from the top reaches K) -- 3
 // passes of 5 barriers instead of the 8 bisection passes' ~2.5 us each (profiles/sampler_r6.txt).
+// `qthr` receives the threshold's 24-bit code: sample_quant(x) > qthr <=> x lies strictly above the K-th value's
+// quantisation cell (the values inside the cell are tied with it at this resolution); 0 when all are kept.
 __device__ __forceinline__ int block_excl_scan(int c, int* s_w, int& total);
+__device__ __forceinline__ int sample_quant(float x, float lo, float scale) {
+  return x >= lo ? min((int)((x - lo) * scale), 16777215) : -1;
+}
 template <int N>
-__device__ float topk_threshold(const float (&v)[N], float hi, float span, int K, float* /*red*/) {
+__device__ float topk_threshold(const float (&v)[N], float hi, float span, int K, float* /*red*/, int& qthr) {
   __shared__ int s_hist[SAMPLE_THREADS];
   __shared__ int s_w2[16], s_sel[2];
   static_assert(SAMPLE_THREADS == 256, "one histogram bin per thread");
@@ -426,8 +431,9 @@ __device__ float topk_threshold(const float (&v)[N], float hi, float span, int K
   const float lo = hi - span, scale = 16777216.f / span;
   int u[N];
 #pragma unroll
-  for (int j = 0; j < N; ++j) u[j] = v[j] >= lo ? min((int)((v[j] - lo) * scale), 16777215) : -1;
+  for (int j = 0; j < N; ++j) u[j] = sample_quant(v[j], lo, scale);
   int prefix = 0, above = 0;
+  qthr = 0;
 #pragma unroll 1
   for (int pass = 0; pass < 3; ++pass) {
     const int shift = 16 - 8 * pass;
@@ -453,6 +459,7 @@ __device__ float topk_threshold(const float (&v)[N], float hi, float span, int K
     above = s_sel[1];
     __syncthreads();  // (s_sel / s_hist rewritten by the next pass)
   }
+  qthr = prefix;
   return lo + (float)prefix / scale - span * 1e-7f;
 }
 
@@ -570,7 +577,9 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_kernel(SampleArgs a) {
     pub = block_argmax(g, sv, si);
   }
   if (filt) {  // local top-K candidates (the global top-K is a subset of their union)
-    const float thr = m.v > -INFINITY ? topk_threshold(v, m.v, 30.f * temp + 1.f, K, red) : INFINITY;
+    const float span = 30.f * temp + 1.f;
+    int qthr = 0;
+    const float thr = m.v > -INFINITY ? topk_threshold(v, m.v, span, K, red, qthr) : INFINITY;
     stamp(2);
     // (slots by a block prefix sum in (thread, j) order: the candidate order -- and so every float sum over
     // candidates below -- is the same on every run)
@@ -579,16 +588,35 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_kernel(SampleArgs a) {
     for (int j = 0; j < SAMPLE_PER_THREAD; ++j) c += (v[j] >= thr && v[j] > -INFINITY) ? 1 : 0;
     int total;
     int k = block_excl_scan(c, s_w, total);
+    auto publish = [&](int slot, int j) __attribute__((always_inline)) {
+      if (slot < SAMPLE_KCAP) {
+        const size_t o = ((size_t)b * NS + slice) * SAMPLE_KCAP + slot;
+        __hip_atomic_store(w.cand_v + o, v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(w.cand_i + o, slice * SAMPLE_SLICE + j * SAMPLE_THREADS + tid, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+      }
+    };
+    if (total <= SAMPLE_KCAP) {
 #pragma unroll
-    for (int j = 0; j < SAMPLE_PER_THREAD; ++j) {
-      if (v[j] >= thr && v[j] > -INFINITY) {
-        if (k < SAMPLE_KCAP) {
-          const size_t o = ((size_t)b * NS + slice) * SAMPLE_KCAP + k;
-          __hip_atomic_store(w.cand_v + o, v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(w.cand_i + o, slice * SAMPLE_SLICE + j * SAMPLE_THREADS + tid, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
+      for (int j = 0; j < SAMPLE_PER_THREAD; ++j)
+        if (v[j] >= thr && v[j] > -INFINITY) publish(k++, j);
+    } else {
+      // more than the slots hold: the K-th value is tied (to the threshold's resolution) many times.  Fewer
+      // than K values lie strictly above its cell; they take the first slots, the tied ones what is left --
+      // a token above the K-th value is never displaced by tokens tied at it (ops.h)
+      const float lo = m.v - span, scale = 16777216.f / span;
+      int ca = 0;
+#pragma unroll
+      for (int j = 0; j < SAMPLE_PER_THREAD; ++j) ca += (v[j] >= thr && sample_quant(v[j], lo, scale) > qthr) ? 1 : 0;
+      int na;
+      int ka = block_excl_scan(ca, s_w, na);
+      int kt = na + (k - ka);  // (k counts both kinds before this thread)
+#pragma unroll
+      for (int j = 0; j < SAMPLE_PER_THREAD; ++j) {
+        if (v[j] >= thr && v[j] > -INFINITY) {
+          if (sample_quant(v[j], lo, scale) > qthr) publish(ka++, j);
+          else publish(kt++, j);
         }
-        ++k;
       }
     }
     if (tid == 0) s_cnt = total;
@@ -632,26 +660,73 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_kernel(SampleArgs a) {
       for (int s = 0; s < NS; ++s) s_off[s + 1] += s_off[s];
     }
     __syncthreads();
-    const int nc = min(s_off[NS], SAMPLE_MAX_CAND);
-    for (int o = tid; o < nc; o += SAMPLE_THREADS) {
-      int s = 0;
-      while (s + 1 < NS && s_off[s + 1] <= o) ++s;
-      const size_t g = ((size_t)b * NS + s) * SAMPLE_KCAP + (o - s_off[s]);
-      s_kv[o] = ldf(w.cand_v + g);
-      s_ki[o] = ldi(w.cand_i + g);
-    }
-    __syncthreads();
+    // The table holds SAMPLE_MAX_CAND candidates; the slices publish up to NS * SAMPLE_KCAP (4x that at 64
+    // slices).  Rounds: as many further slices as fit go in behind what the table carries, the top-K
+    // threshold of the table is taken, and -- while slices remain -- the table is compacted to the values at
+    // or above it: the running top-K.  A threshold over part of the candidates is never above the one over
+    // all of them and every round quantises on the same grid (M, span), so the last round's threshold and
+    // survivors are those of one pass over all candidates.  Up to SAMPLE_MAX_CAND candidates (every V <=
+    // 65536, and top-k <= 4096 / NS above that) it is one round: the gather and the threshold as before.
+    const float M = r.v;  // the global max is a candidate of its slice, and stays in the table
+    const float span = 30.f * temp + 1.f;
     float cv[SAMPLE_MAX_CAND / SAMPLE_THREADS];
+    float thr;
+    int nc = 0;
+#pragma unroll 1
+    for (int s0 = 0;;) {
+      int s1 = s0 + 1;  // (one slice always fits: the carry is at most SAMPLE_MAX_CAND - SAMPLE_KCAP)
+      while (s1 < NS && nc + s_off[s1 + 1] - s_off[s0] <= SAMPLE_MAX_CAND) ++s1;
+      const int base = s_off[s0], add = s_off[s1] - base;
+      for (int o = tid; o < add; o += SAMPLE_THREADS) {
+        int s = s0;
+        while (s + 1 < s1 && s_off[s + 1] - base <= o) ++s;
+        const size_t g = ((size_t)b * NS + s) * SAMPLE_KCAP + (o - (s_off[s] - base));
+        s_kv[nc + o] = ldf(w.cand_v + g);
+        s_ki[nc + o] = ldi(w.cand_i + g);
+      }
+      nc += add;
+      s0 = s1;
+      __syncthreads();
 #pragma unroll
-    for (int j = 0; j < SAMPLE_MAX_CAND / SAMPLE_THREADS; ++j) {
-      const int o = j * SAMPLE_THREADS + tid;
-      cv[j] = o < nc ? s_kv[o] : -INFINITY;
+      for (int j = 0; j < SAMPLE_MAX_CAND / SAMPLE_THREADS; ++j) {
+        const int o = j * SAMPLE_THREADS + tid;
+        cv[j] = o < nc ? s_kv[o] : -INFINITY;
+      }
+      stamp(6);
+      int qthr;
+      thr = topk_threshold(cv, M, span, K, red, qthr);
+      if (s0 >= NS) break;
+      // carry: the values strictly above the threshold's cell first (fewer than K), then the ones tied in it
+      // while they fit -- both in (thread, j) order, the same on every run
+      const float lo = M - span, scale = 16777216.f / span;
+      int ci[SAMPLE_MAX_CAND / SAMPLE_THREADS];
+      int c = 0, ca = 0;
+#pragma unroll
+      for (int j = 0; j < SAMPLE_MAX_CAND / SAMPLE_THREADS; ++j) {
+        ci[j] = s_ki[j * SAMPLE_THREADS + tid];
+        const bool in = cv[j] >= thr && cv[j] > -INFINITY;
+        c += in ? 1 : 0;
+        ca += (in && sample_quant(cv[j], lo, scale) > qthr) ? 1 : 0;
+      }
+      int n, na;
+      const int k = block_excl_scan(c, s_w, n);
+      int ka = block_excl_scan(ca, s_w, na);  // (its first barrier: every thread has read its s_ki entries)
+      int kt = na + (k - ka);
+#pragma unroll
+      for (int j = 0; j < SAMPLE_MAX_CAND / SAMPLE_THREADS; ++j) {
+        if (cv[j] >= thr && cv[j] > -INFINITY) {
+          const int o = sample_quant(cv[j], lo, scale) > qthr ? ka++ : kt++;
+          if (o < SAMPLE_MAX_CAND - SAMPLE_KCAP) {
+            s_kv[o] = cv[j];
+            s_ki[o] = ci[j];
+          }
+        }
+      }
+      nc = min(n, SAMPLE_MAX_CAND - SAMPLE_KCAP);
+      __syncthreads();
     }
-    stamp(6);
-    const float M = r.v;  // the global max is a candidate of its slice
-    const float thr = topk_threshold(cv, M, 30.f * temp + 1.f, K, red);
     stamp(7);
-    // survivors: top-K (ties kept), then the nucleus over them.  Round 6: the survivors are compacted
+    // survivors: top-K (ties kept, as far as the slices and the carry held them), then the nucleus over them.  Round 6: the survivors are compacted
     // (block prefix sum, deterministic order) with their weights e = exp((v - M) / T) computed once, and
     // each survivor's rank-ordered mass before it sums over the S survivors only -- the old loop re-ran
     // exp over all nc candidates per survivor (~100 us per sampled token at nc ~ 2k, profiles/)

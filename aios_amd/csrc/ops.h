@@ -164,6 +164,15 @@ bool attn_prefill_supports(int n_heads, int n_kv_heads, int head_dim);  // keys 
 // exp((l_i - M) / T) >= min_p[b], M the largest allowed penalised logit (a ratio test on the tempered
 // distribution: it intersects with the nucleus, nothing is renormalised before it; <= 0: off; greedy
 // ignores it).  min-p with top-k and top-p both off works on the top-256 logits, like top-p alone.
+// Top-K, K = min(top_k, 256) or 256: a token stays if l >= the K-th largest allowed logit, compared on a
+// grid of (30 T + 1) * 2^-24 (values within a cell of the K-th count as tied with it and stay).  Ties: a
+// token strictly above the K-th value is never displaced by tokens tied at it -- a 4096-token slice
+// publishes at most 256 candidates and the merge carries at most 3840 from round to round, and what either
+// drops beyond that comes from the group tied at the threshold only (the last of it in thread order).
+// Capacity: every V up to SAMPLE_MAX_V with every K up to 256 -- the merge folds the slices' candidates (up
+// to 256 * V / 4096) through its 4096-entry table in rounds (one round up to 4096 candidates, i.e. every
+// V <= 65536), in a fixed order: the same logits, settings and RNG key give the same token on every run.
+// tests/sampler_oracle.py is this rule in float64.
 constexpr int SAMPLE_PEN_MAX = 256;  // longest penalty window (one entry per sampler thread)
 constexpr int SAMPLE_MAX_V = 262144; // largest vocabulary launch_sample takes (64 slices of 4096)
 struct SampleArgs {

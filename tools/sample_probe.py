@@ -1,8 +1,11 @@
-"""Device sampler timing (aios::sample_kernel) per configuration: B = 1 row of a 32000-logit vocabulary,
-greedy / temperature / top-k / top-p, with and without a grammar mask (allowed-token bitmap).
+"""Device sampler timing (aios::sample_kernel) per configuration: B = 1 row of a 32000-logit vocabulary
+(--vocab: another size, up to 262144; past 65536 top-p alone publishes more candidates than the merge's
+table holds and the merge runs in rounds), greedy / temperature / top-k / top-p, with and without a grammar
+mask (allowed-token bitmap).
 
-  python tools/sample_probe.py
+  python tools/sample_probe.py [--vocab 128256]
 """
+import argparse
 import json
 import os
 import sys
@@ -14,9 +17,11 @@ from aios_amd.runtime import native
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--vocab", type=int, default=32000)
     only = os.environ.get("SAMPLE_ONLY", "")
     E = native.require()
-    V, B = 32000, 1
+    V, B = ap.parse_args().vocab, 1
     st = torch.cuda.current_stream().cuda_stream
     g = torch.Generator().manual_seed(0)
     logits = (torch.randn(B, V, generator=g) * 3).cuda()
@@ -52,7 +57,7 @@ def main():
             run()
         e1.record()
         torch.cuda.synchronize()
-        row = {"config": name, "us": round(e0.elapsed_time(e1) * 1e3 / 200, 2), "token": int(tok[0])}
+        row = {"config": name, "vocab": V, "us": round(e0.elapsed_time(e1) * 1e3 / 200, 2), "token": int(tok[0])}
         # phase stamps (s_memrealtime, 100 MHz) of one launch: per slice workgroup, us from the first entry
         ns = (V + 4095) // 4096
         ts = torch.zeros(B * ns * 16, dtype=torch.int64, device="cuda")
