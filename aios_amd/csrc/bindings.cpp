@@ -266,6 +266,22 @@ PYBIND11_MODULE(_engine, m) {
       .def("set_sample_processors", &Engine::set_sample_processors, py::arg("min_p"), py::arg("repeat_penalty"),
            py::arg("presence_penalty"), py::arg("frequency_penalty"), py::arg("recent"),
            py::call_guard<py::gil_scoped_release>())
+      .def("set_logprobs", &Engine::set_logprobs, py::arg("top_n"))
+      .def("last_logprobs",
+           [](const Engine& e) -> py::object {
+             // () when the last sampler launch had none staged, else (token_lp [B], ids [B][LOGPROB_MAX_TOP],
+             // lps [B][LOGPROB_MAX_TOP]); rows that were off: NaN, -1, -inf
+             const Engine::Logprobs r = e.last_logprobs();
+             if (r.top_n.empty()) return py::tuple(0);
+             const py::ssize_t B = (py::ssize_t)r.top_n.size();
+             py::array_t<float> lp(B);
+             py::array_t<int> ids({B, (py::ssize_t)LOGPROB_MAX_TOP});
+             py::array_t<float> lps({B, (py::ssize_t)LOGPROB_MAX_TOP});
+             std::memcpy(lp.mutable_data(), r.token_lp.data(), r.token_lp.size() * 4);
+             std::memcpy(ids.mutable_data(), r.ids.data(), r.ids.size() * 4);
+             std::memcpy(lps.mutable_data(), r.lps.data(), r.lps.size() * 4);
+             return py::make_tuple(lp, ids, lps);
+           })
       .def("sample_first",
            [](Engine& e, int pos, float temperature, int top_k, float top_p, uint64_t seed, py::bytes mask) {
              std::string m = mask;
@@ -705,6 +721,44 @@ PYBIND11_MODULE(_engine, m) {
         py::arg("seed"), py::arg("tokens"), py::arg("pos"), py::arg("mask"), py::arg("st"), py::arg("top_p") = 0,
         py::arg("ts") = 0, py::arg("min_p") = 0, py::arg("pen_tokens") = 0, py::arg("pen_stride") = 0,
         py::arg("repeat_penalty") = 0, py::arg("presence_penalty") = 0, py::arg("frequency_penalty") = 0);
+  m.attr("LOGPROB_MAX_TOP") = LOGPROB_MAX_TOP;
+  m.def("logprobs",
+        [](uintptr_t logits, int ldl, int B, int V, uintptr_t tokens, uintptr_t top_n, uintptr_t out_lp, uintptr_t out_id,
+           uintptr_t st) {
+          // grow-on-demand scratch for the raw-op binding (the engine owns its own); out_lp / out_id:
+          // [B][LOGPROB_MAX_TOP + 1]
+          static void* ws = nullptr;
+          static size_t ws_bytes = 0;
+          static int* cnt = nullptr;
+          static int cnt_len = 0;
+          if (B < 1 || V < 1 || V > SAMPLE_MAX_V)  // (before the sizes below are taken from them)
+            throw std::runtime_error("logprobs: batch or vocabulary out of range (V <= " + std::to_string(SAMPLE_MAX_V) + ")");
+          const size_t need = logprob_ws_bytes(B, V);
+          if (need > ws_bytes) {
+            if (ws) HIP_CHECK(hipFree(ws));
+            ws = nullptr;
+            ws_bytes = 0;
+            HIP_CHECK(hipMalloc(&ws, need));
+            ws_bytes = need;
+          }
+          if (B > cnt_len) {
+            if (cnt) HIP_CHECK(hipFree(cnt));
+            cnt = nullptr;
+            cnt_len = 0;
+            HIP_CHECK(hipMalloc(&cnt, (size_t)B * 4));
+            HIP_CHECK(hipMemset(cnt, 0, (size_t)B * 4));
+            cnt_len = B;
+          }
+          LogprobArgs a;
+          std::memset(&a, 0, sizeof(a));
+          a.logits = (const float*)logits; a.ldl = ldl; a.B = B; a.V = V;
+          a.tokens = (const int*)tokens; a.top_n = (const int*)top_n;
+          a.out_lp = (float*)out_lp; a.out_id = (int*)out_id;
+          a.ws = ws; a.ws_bytes = ws_bytes; a.counters = cnt;
+          launch_logprobs(a, S(st));
+        },
+        py::arg("logits"), py::arg("ldl"), py::arg("B"), py::arg("V"), py::arg("tokens"), py::arg("top_n"),
+        py::arg("out_lp"), py::arg("out_id"), py::arg("st"));
   m.def("gemm",
         [](uintptr_t A, int lda, PyQMatrix* w, int M, uintptr_t C, int ldc, int accumulate, uintptr_t st) {
           GemmArgs a;

@@ -11,6 +11,7 @@
 #pragma once
 #include <map>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -150,6 +151,25 @@ class Engine {
                              const std::vector<float>& presence_penalty, const std::vector<float>& frequency_penalty,
                              const std::vector<std::vector<int>>& recent);
 
+  // Per-token log-probabilities (ops.h LogprobArgs: the RAW distribution, before penalties, mask and
+  // temperature) of the NEXT sampler launch only -- decode, decode_sample, sample_first or resample,
+  // whichever comes first -- and dropped after it: set_sample_processors' contract.  One entry per row of
+  // that launch: the alternatives wanted, 0..LOGPROB_MAX_TOP, or < 0 for a row that reports nothing.
+  // The logprob launch follows the sampler on the stream, reads the tokens it wrote, and its outputs
+  // reach pinned memory before the step's tokens do; decode() with logprobs staged runs the forward
+  // graph and an eager sampler, as with staged processors.  Single-GPU engines only: a vocab-parallel
+  // lm_head shards the row.
+  void set_logprobs(const std::vector<int>& top_n);
+  // what the last sampler launch reported (call after its tokens were returned / collected); every vector
+  // empty when that launch had nothing staged.  Rows that were off: token_lp NaN, ids -1, lps -inf.
+  struct Logprobs {
+    std::vector<int> top_n;       // [B] as staged
+    std::vector<float> token_lp;  // [B] logprob of the sampled token
+    std::vector<int> ids;         // [B][LOGPROB_MAX_TOP] alternatives, best first; -1 past the row's top_n
+    std::vector<float> lps;       // [B][LOGPROB_MAX_TOP]
+  };
+  Logprobs last_logprobs() const;
+
   // Device-resident greedy generation for benchmarking: runs n_steps decode steps for B
   // sequences without host synchronisation (tokens fed back on device, graph replay when
   // use_graph).  Sequences must already be prefilled to positions pos[b].
@@ -218,6 +238,28 @@ class Engine {
   char* h_proc_ = nullptr;               // pinned staging: [4][max_batch] floats | [rows][stride] window ints
   char* d_proc_ = nullptr;
   int proc_rows_ = 0, proc_stride_ = 0;  // rows staged (0: none) and their window stride
+  void take_logprobs(int B);             // after a B-row sampler launch: the staged logprob launch + its copy
+  int lp_rows_ = 0;                      // rows staged by set_logprobs (0: none)
+  // A sampler-launching call's hold on the staged logprobs, taken before it enqueues anything: refuses (and
+  // drops) a staging made for another batch size, and drops the staging when the call ends, however it
+  // ends -- a call that throws half way never leaves it to a later, unrelated launch.
+  struct LogprobStage {
+    int& rows;
+    LogprobStage(int& staged, int B, const char* who) : rows(staged) {
+      if (rows && rows != B) {
+        rows = 0;
+        throw std::runtime_error(std::string(who) + ": logprobs staged for another batch size");
+      }
+    }
+    ~LogprobStage() { rows = 0; }
+  };
+  std::vector<int> lp_last_;             // top_n of the rows the last sampler launch reported (empty: none)
+  char* h_lp_ = nullptr;                 // pinned: [max_batch] top_n | the device output block's mirror
+  char* d_lp_out_ = nullptr;             // [max_batch][LOGPROB_ROW] floats | [max_batch][LOGPROB_ROW] ids
+  int* d_lp_topn_ = nullptr;
+  void* lp_ws_ = nullptr;
+  size_t lp_ws_bytes_ = 0;
+  int* lp_cnt_ = nullptr;
   hipGraphExec_t forward_graph(int B);
   int cus_ = 0;                          // CUs of the stream's mask (0: the whole device)
   int kv_es_ = 2;                        // bytes per KV element (2 bf16, 1 fp8)

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstring>
 #include <cmath>
+#include <limits>
 #include <regex>
 #include <sstream>
 
@@ -104,6 +105,7 @@ Engine::~Engine() {
   if (h_tok_out_) hipHostFree(h_tok_out_);
   if (h_mask_) hipHostFree(h_mask_);
   if (h_proc_) hipHostFree(h_proc_);
+  if (h_lp_) hipHostFree(h_lp_);
   if (pipe_ev_) hipEventDestroy(pipe_ev_);
   if (stream_) hipStreamDestroy(stream_);
 }
@@ -586,6 +588,19 @@ void Engine::finalize() {
   sample_ws_ = dmalloc(sample_ws_bytes_);
   ws += sample_ws_bytes_;
   sample_cnt_ = ibuf(Bm);
+  {
+    // per-token logprobs (set_logprobs): slice workspace + tickets, and per row LOGPROB_ROW floats and ids,
+    // device block [Bm rows of floats | Bm rows of ids] mirrored by a pinned one ([top_n | floats | ids])
+    lp_ws_bytes_ = logprob_ws_bytes(Bm, V);
+    lp_ws_ = dmalloc(lp_ws_bytes_);
+    ws += lp_ws_bytes_;
+    lp_cnt_ = ibuf(Bm);
+    d_lp_topn_ = ibuf(Bm);
+    const size_t ob = (size_t)Bm * LOGPROB_ROW * 8;
+    d_lp_out_ = (char*)dmalloc(ob);
+    ws += ob;
+    HIP_CHECK(hipHostMalloc((void**)&h_lp_, (size_t)Bm * 4 + ob, hipHostMallocDefault));
+  }
   d_history_ = ibuf((size_t)Bm * (cfg_.max_ctx + 1));
   const int R = prefill_rows_;
   pf_x_ = fbuf((size_t)R * d);
@@ -1217,6 +1232,63 @@ void Engine::take_processors(SampleArgs& s, int B) {
   s.pen_stride = proc_stride_;
 }
 
+void Engine::set_logprobs(const std::vector<int>& top_n) {
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  if (cfg_.tp_size > 1) throw std::runtime_error("set_logprobs: not available on a tensor-parallel engine");
+  const int B = (int)top_n.size();
+  if (B < 1 || B > cfg_.max_batch) throw std::runtime_error("set_logprobs: batch out of range");
+  for (int n : top_n)
+    if (n > LOGPROB_MAX_TOP) throw std::runtime_error("set_logprobs: top_n above " + std::to_string(LOGPROB_MAX_TOP));
+  // (one pinned buffer, h_proc_'s rule: the previous step's upload ran before the sampler whose token the
+  // host already collected)
+  int* hn = (int*)h_lp_;
+  for (int b = 0; b < B; ++b) hn[b] = top_n[b] < 0 ? -1 : top_n[b];
+  lp_rows_ = B;
+}
+
+// after a B-row sampler launch: the staged logprob launch over the tokens it wrote and the copy of its
+// outputs to pinned memory (valid once the stream reaches the caller's synchronisation point); nothing
+// staged: last_logprobs() is empty
+void Engine::take_logprobs(int B) {
+  lp_last_.clear();
+  if (!lp_rows_) return;
+  const int rows = lp_rows_, Bm = cfg_.max_batch;
+  lp_rows_ = 0;  // one shot, also when the launch does not happen
+  if (rows != B) throw std::runtime_error("logprobs staged for another batch size");
+  const int* hn = (const int*)h_lp_;
+  HIP_CHECK(hipMemcpyAsync(d_lp_topn_, hn, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  LogprobArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.logits = logits_; a.ldl = cfg_.vocab_size; a.B = B; a.V = cfg_.vocab_size;
+  a.tokens = d_tokens_; a.top_n = d_lp_topn_;
+  a.out_lp = (float*)d_lp_out_; a.out_id = (int*)(d_lp_out_ + (size_t)Bm * LOGPROB_ROW * 4);
+  a.ws = lp_ws_; a.ws_bytes = lp_ws_bytes_; a.counters = lp_cnt_;
+  launch_logprobs(a, stream_);
+  // one copy: every row of floats and the first B rows of ids
+  HIP_CHECK(hipMemcpyAsync(h_lp_ + (size_t)Bm * 4, d_lp_out_, (size_t)(Bm + B) * LOGPROB_ROW * 4, hipMemcpyDeviceToHost,
+                           stream_));
+  lp_last_.assign(hn, hn + B);
+}
+
+Engine::Logprobs Engine::last_logprobs() const {
+  Logprobs r;
+  const int B = (int)lp_last_.size(), Bm = cfg_.max_batch;
+  if (!B) return r;
+  const float* hl = (const float*)(h_lp_ + (size_t)Bm * 4);
+  const int* hi = (const int*)(hl + (size_t)Bm * LOGPROB_ROW);
+  r.top_n = lp_last_;
+  r.token_lp.assign(B, std::numeric_limits<float>::quiet_NaN());
+  r.ids.assign((size_t)B * LOGPROB_MAX_TOP, -1);
+  r.lps.assign((size_t)B * LOGPROB_MAX_TOP, -std::numeric_limits<float>::infinity());
+  for (int b = 0; b < B; ++b) {
+    if (lp_last_[b] < 0) continue;  // row off: the kernel wrote nothing
+    r.token_lp[b] = hl[(size_t)b * LOGPROB_ROW];
+    std::copy(hi + (size_t)b * LOGPROB_ROW + 1, hi + (size_t)(b + 1) * LOGPROB_ROW, r.ids.begin() + (size_t)b * LOGPROB_MAX_TOP);
+    std::copy(hl + (size_t)b * LOGPROB_ROW + 1, hl + (size_t)(b + 1) * LOGPROB_ROW, r.lps.begin() + (size_t)b * LOGPROB_MAX_TOP);
+  }
+  return r;
+}
+
 void Engine::enqueue_sample(int B, bool processors) {
   const int V = cfg_.vocab_size;
   SampleArgs s;
@@ -1528,6 +1600,7 @@ std::vector<int> Engine::decode(const std::vector<int>& slots, const std::vector
   if (!finalized_) throw std::runtime_error("engine not finalized");
   HIP_CHECK(hipSetDevice(cfg_.device));
   const int B = (int)slots.size();
+  const LogprobStage lp_stage(lp_rows_, B, "decode");  // (before the step changes any state)
   if (!seeds.empty() && (int)seeds.size() != B) throw std::runtime_error("decode: seeds size mismatch");
   if (B < 1 || B > cfg_.max_batch) throw std::runtime_error("decode: batch out of range");
   if ((int)tokens.size() != B || (int)pos.size() != B) throw std::runtime_error("decode: size mismatch");
@@ -1567,9 +1640,9 @@ std::vector<int> Engine::decode(const std::vector<int>& slots, const std::vector
     nbytes = par_mask_off_ + mbytes;
   }
   HIP_CHECK(hipMemcpyAsync(d_par_, h_par_, nbytes, hipMemcpyHostToDevice, stream_));
-  if (proc_rows_) {
-    // staged logit processors: the forward graph and an eager sampler, as the pipelined path runs a
-    // step -- the captured (B, masked) step graphs never see them
+  if (proc_rows_ || lp_rows_) {
+    // staged logit processors / logprobs: the forward graph and an eager sampler (and logprob launch), as
+    // the pipelined path runs a step -- the captured (B, masked) step graphs never see them
     for (int b = 0; b < B; ++b) {
       kv_prepare_write(row_slots_[b], row_pos_[b], std::min(row_pos_[b] + 1, cfg_.max_ctx));
       row_pos_[b] = std::min(row_pos_[b] + 1, cfg_.max_ctx);
@@ -1578,6 +1651,7 @@ std::vector<int> Engine::decode(const std::vector<int>& slots, const std::vector
     HIP_CHECK(hipGraphLaunch(forward_graph(B), stream_));
     try {
       enqueue_sample(B, true);
+      take_logprobs(B);
     } catch (...) {
       sample_mask_ = false;
       throw;
@@ -1596,6 +1670,7 @@ std::vector<int> Engine::resample(int B, const std::vector<float>& temperature, 
   const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
   // re-run only the sampler on the logits of the last step (grammar fast path: the unmasked
   // sample was rejected on the host)
+  const LogprobStage lp_stage(lp_rows_, B, "resample");  // (before the sampler is enqueued)
   HIP_CHECK(hipSetDevice(cfg_.device));
   std::vector<float> temps(B, 0.f);
   std::vector<int> tks(B, 0);
@@ -1625,6 +1700,7 @@ std::vector<int> Engine::resample(int B, const std::vector<float>& temperature, 
   take_processors(s, B);
   // pos was advanced by the step: RNG key uses pos[b] (a different stream than the first sample)
   launch_sample(s, stream_);
+  take_logprobs(B);
   std::vector<int> out(B);
   HIP_CHECK(hipMemcpyAsync(out.data(), d_tokens_, B * 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
@@ -1641,6 +1717,7 @@ int Engine::sample_first(int pos, float temperature, int top_k, float top_p, uin
                          const std::vector<uint8_t>& mask) {
   const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
   if (!finalized_) throw std::runtime_error("engine not finalized");
+  const LogprobStage lp_stage(lp_rows_, 1, "sample_first");  // (before the sampler is enqueued)
   HIP_CHECK(hipSetDevice(cfg_.device));
   const size_t mbytes = (size_t)((cfg_.vocab_size + 7) / 8);
   if (!mask.empty() && mask.size() != mbytes) throw std::runtime_error("sample_first: mask size mismatch");
@@ -1660,6 +1737,7 @@ int Engine::sample_first(int pos, float temperature, int top_k, float top_p, uin
   s.top_p = d_topp_; s.ws = sample_ws_; s.ws_bytes = sample_ws_bytes_; s.counters = sample_cnt_;
   take_processors(s, 1);
   launch_sample(s, stream_);
+  take_logprobs(1);
   int out = 0;
   HIP_CHECK(hipMemcpyAsync(&out, d_tokens_, 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
@@ -1707,6 +1785,8 @@ void Engine::decode_loop_run(int B, int n_steps, bool use_graph) {
   TraceRange tr(use_graph ? "aios.decode_graph_replay" : "aios.decode_eager");
   HIP_CHECK(hipSetDevice(cfg_.device));
   if ((int)row_slots_.size() < B) throw std::runtime_error("decode_loop_run: rows not prepared");
+  lp_last_.clear();  // (captured steps never carry a logprob launch: a staging is dropped, not kept for later)
+  lp_rows_ = 0;
   // map (and un-share) the blocks the n steps will write, before any of them is enqueued
   for (int b = 0; b < B; ++b) {
     kv_prepare_write(row_slots_[b], row_pos_[b], std::min(row_pos_[b] + n_steps, cfg_.max_ctx));
@@ -1822,6 +1902,7 @@ void Engine::decode_sample(const std::vector<uint8_t>& mask) {
   const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
   const int B = pipe_B_;
   if (B < 1) throw std::runtime_error("decode_sample: no submitted step");
+  const LogprobStage lp_stage(lp_rows_, B, "decode_sample");  // (before the sampler is enqueued)
   HIP_CHECK(hipSetDevice(cfg_.device));
   const size_t mbytes = (size_t)B * ((cfg_.vocab_size + 7) / 8);
   if (!mask.empty()) {
@@ -1834,6 +1915,7 @@ void Engine::decode_sample(const std::vector<uint8_t>& mask) {
   sample_mask_ = !mask.empty();
   try {
     enqueue_sample(B, true);
+    take_logprobs(B);
   } catch (...) {
     sample_mask_ = false;
     throw;

@@ -207,6 +207,35 @@ struct SampleArgs {
 void launch_sample(const SampleArgs& a, hipStream_t st);
 size_t sample_ws_bytes(int B, int V);
 
+// Per-token log-probabilities of the model's RAW distribution (before penalties, the grammar mask and
+// temperature), for the tokens a sampler launch just wrote.  Per row b with top_n[b] >= 0:
+//   lse = log sum_i exp(l[b][i]) over i in [0, V);  out_lp[b][0] = l[b][t] - lse, out_id[b][0] = t, t = tokens[b]
+//   clamped to [0, V);
+//   out_id[b][1..n], out_lp[b][1..n], n = min(top_n[b], V): the n largest logits, value descending, ties by
+//   the lower token id, each as l - lse; the entries behind them get id -1 and logprob -inf.
+// Selection compares the fp32 values as they are (no arithmetic), so the ids are exact; a -inf logit has
+// logprob -inf and may close the list.  A row that is all -inf or holds a NaN is unspecified.
+// top_n[b] < 0: row off -- its outputs are not written.  tokens[] lives on the device, written by the sampler
+// launch in front (which only writes ids in [0, V)); no launcher sees it on the host, so nothing throws for
+// an id outside [0, V): only the kernel's clamp keeps the read in bounds, and out_id[b][0] shows the id used.
+// The host rule (runtime/sampler.py: logprobs), which has the token, raises.  kernels/logprobs.hip; tests/logprob_oracle.py is this rule in float64.
+constexpr int LOGPROB_MAX_TOP = 20;  // alternatives per token (OpenAI's top_logprobs cap)
+constexpr int LOGPROB_ROW = LOGPROB_MAX_TOP + 1;  // entries per output row: the token, then the alternatives
+struct LogprobArgs {
+  const float* logits;
+  int ldl;
+  int B, V;              // V <= SAMPLE_MAX_V
+  const int* tokens;     // [B] the sampled tokens
+  const int* top_n;      // [B] alternatives wanted, 0..LOGPROB_MAX_TOP; < 0: row off
+  float* out_lp;         // [B][LOGPROB_ROW]
+  int* out_id;           // [B][LOGPROB_ROW]
+  void* ws;              // logprob_ws_bytes(B, V) scratch (slice maxima, sums and candidates)
+  size_t ws_bytes;
+  int* counters;         // [B] arrival tickets, zero-initialised, self re-arming
+};
+void launch_logprobs(const LogprobArgs& a, hipStream_t st);
+size_t logprob_ws_bytes(int B, int V);
+
 // ---- MFMA GEMM (prefill) ----------------------------------------------------------------------
 // C[M][N] (fp32, epilogue) = A[M][K] (bf16) x W[N][K]^T (quantized, dequantized tile-wise in LDS)
 struct GemmArgs {

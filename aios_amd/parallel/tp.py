@@ -335,6 +335,11 @@ class TPEngine:
             # not broadcast to the workers, whose samplers run in lock step with the leader's: a
             # tensor-parallel tier has no logit processors (the scheduler logs that once)
             raise AttributeError(name)
+        if name in ("set_logprobs", "last_logprobs"):
+            # a tensor-parallel tier has no per-token logprobs (with a vocab-parallel lm_head the row is
+            # sharded; the shard's own Engine.set_logprobs throws): the scheduler sees no such method,
+            # refuses the request alone, and the HTTP endpoint answers 400
+            raise AttributeError(name)
         attr = getattr(self._eng, name)
         if name not in self._FORWARD or not callable(attr):
             return attr

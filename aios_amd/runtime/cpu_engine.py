@@ -45,6 +45,8 @@ class CpuEngine:
         self.kv_bytes = 2 * c.n_layers * max_slots * max_ctx * c.n_kv_heads * c.head_dim * 4
         self.last: Optional[np.ndarray] = None
         self._proc = None  # set_sample_processors: per-row processors of the next sampler call only
+        self._lp = None    # set_logprobs: per-row top_n of the next sampler call only
+        self._lp_out = ()  # last_logprobs: what the last sampler call reported
 
     @classmethod
     def from_gguf(cls, path: str, max_ctx: int = 2048, max_slots: int = 4, max_batch: int = 4,
@@ -98,6 +100,41 @@ class CpuEngine:
         self._proc = (list(min_p), list(repeat_penalty), list(presence_penalty), list(frequency_penalty),
                       [list(w) for w in recent])
 
+    def set_logprobs(self, top_n):
+        """Per-row alternatives wanted (0..LOGPROB_MAX_TOP, < 0: row off) from the NEXT sampler call
+        (decode or sample_first), then dropped -- the native Engine's contract."""
+        top_n = [int(n) for n in top_n]
+        if not 1 <= len(top_n) <= self.config.max_batch:
+            raise ValueError("set_logprobs: batch out of range")
+        if any(n > host_sampler.LOGPROB_MAX_TOP for n in top_n):
+            raise ValueError(f"set_logprobs: top_n above {host_sampler.LOGPROB_MAX_TOP}")
+        self._lp = top_n
+
+    def _take_logprobs(self, rows, toks):
+        """after a sampler call over the raw logits `rows` that chose `toks`: the staged report"""
+        top_n, self._lp = self._lp, None
+        self._lp_out = ()
+        if top_n is None:
+            return
+        if len(top_n) != len(toks):
+            raise ValueError("logprobs staged for another batch size")
+        K = host_sampler.LOGPROB_MAX_TOP
+        lp = np.full(len(toks), np.nan, np.float64)
+        ids = np.full((len(toks), K), -1, np.int32)
+        lps = np.full((len(toks), K), -np.inf, np.float64)
+        for b, n in enumerate(top_n):
+            if n < 0:
+                continue
+            lp[b], i, x = host_sampler.logprobs(rows[b], toks[b], n)
+            ids[b, :len(i)] = i
+            lps[b, :len(x)] = x
+        self._lp_out = (lp, ids, lps)
+
+    def last_logprobs(self):
+        """() when the last sampler call had none staged, else (token logprob [B], ids [B][20], logprobs
+        [B][20]); rows that were off: NaN, -1, -inf -- the native Engine's shape"""
+        return self._lp_out
+
     def _sample(self, proc, b, logits, t, k, tp, m, rng):
         if proc is None or b >= len(proc[4]):
             return host_sampler.sample(logits, t, k, tp, m, rng)
@@ -125,6 +162,7 @@ class CpuEngine:
             tp = float(top_p[b]) if top_p is not None and b < len(top_p) else 1.0
             out.append(self._sample(proc, b, logits, t, k, tp, m, rng))
         self.last = np.stack(rows) if rows else None
+        self._take_logprobs(rows, out)
         return out
 
     def sample_first(self, pos, temperature, top_k, top_p, seed, mask: bytes = b""):
@@ -132,7 +170,9 @@ class CpuEngine:
         logits = self.last[0]
         rng = np.random.default_rng([int(seed) & 0xFFFFFFFF, int(pos)])
         proc, self._proc = self._proc, None
-        return self._sample(proc, 0, logits, float(temperature), int(top_k), float(top_p), mask or None, rng)
+        tok = self._sample(proc, 0, logits, float(temperature), int(top_k), float(top_p), mask or None, rng)
+        self._take_logprobs([logits], [tok])
+        return tok
 
     def last_logits(self, B: int):
         return self.last[:B].reshape(-1) if self.last is not None else np.zeros(0, np.float32)

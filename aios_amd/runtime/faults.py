@@ -77,7 +77,8 @@ class FaultyEngine:
         return self._engine.decode(*a, **k)
 
     def __getattr__(self, name):
-        # every other attribute is the engine's own (set_sample_processors too: present iff it has it)
+        # every other attribute is the engine's own (set_sample_processors, set_logprobs and last_logprobs
+        # too: present iff it has them)
         attr = getattr(self._engine, name)
         if name == "decode_submit":  # the pipelined decode's step (present iff the engine has it)
             def submit(*a, **k):

@@ -91,6 +91,26 @@ def sample(logits: np.ndarray, temperature: float = 0.0, top_k: int = 0, top_p: 
     return int(rng.choice(p.shape[0], p=p))
 
 
+LOGPROB_MAX_TOP = 20  # alternatives per token (OpenAI's top_logprobs cap; ops.h LOGPROB_MAX_TOP)
+
+
+def logprobs(logits: np.ndarray, token: int, top_n: int = 0):
+    """Per-token log-probabilities of the RAW row (before penalties, mask and temperature), in float64:
+    (logprob of `token`, ids, logprobs) with the min(top_n, V) largest logits, value descending, ties
+    by the lower id -- the device kernel's rule (csrc/ops.h LogprobArgs)."""
+    l = np.asarray(logits, dtype=np.float64)
+    V = l.shape[0]
+    if not 0 <= int(token) < V:
+        raise ValueError(f"logprobs: token {token} outside [0, {V})")
+    if not 0 <= int(top_n) <= LOGPROB_MAX_TOP:
+        raise ValueError(f"logprobs: top_n outside 0..{LOGPROB_MAX_TOP}")
+    m = np.max(l)
+    lse = m + np.log(np.sum(np.exp(l - m)))
+    # (lexsort: last key first -- value descending, then id ascending)
+    ids = np.lexsort((np.arange(V), -l))[:min(int(top_n), V)]
+    return float(l[int(token)] - lse), [int(i) for i in ids], [float(x) for x in l[ids] - lse]
+
+
 def all_allowed(vocab: int) -> bytes:
     m = np.zeros((vocab + 7) // 8, np.uint8) + 0xFF
     return m.tobytes()

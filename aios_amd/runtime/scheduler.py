@@ -67,6 +67,11 @@ class GenRequest:
     repeat_last_n: int = 64           # penalty window: the row's last n tokens, prompt tail included (< 0 or > 256: 256)
     presence_penalty: Optional[float] = None
     frequency_penalty: Optional[float] = None
+    # per-token log-probabilities of the model's RAW distribution (before penalties, the grammar mask and
+    # temperature; runtime/sampler.py: logprobs): the chosen token's, and its top_logprobs (0..20) best
+    # alternatives -- GenResult.logprobs.  The stream callback carries text only.
+    logprobs: bool = False
+    top_logprobs: int = 0
     stop_ids: Optional[List[int]] = None
     on_delta: Optional[Callable[[str], None]] = None
     on_done: Optional[Callable[["GenResult"], None]] = None
@@ -86,11 +91,14 @@ class GenResult:
     latency_ms: float = 0.0
     cached_prompt_tokens: int = 0
     error: str = ""
+    # requests with logprobs=True: one (token id, logprob, [(alternative id, logprob), ...]) per entry of
+    # token_ids, best alternative first; None otherwise
+    logprobs: Optional[list] = None
 
 
 class _Seq:
     __slots__ = ("req", "slot", "pos", "last", "out", "grammar_state", "emitted", "t_first", "cached", "todo",
-                 "p_off", "r_off", "seed", "proc", "pen_n")
+                 "p_off", "r_off", "seed", "proc", "pen_n", "lp_n", "lps")
 
     def __init__(self, req, slot):
         self.req, self.slot = req, slot
@@ -107,6 +115,8 @@ class _Seq:
         self.todo: List[int] = []    # prompt tokens still to prefill
         self.proc = None             # (min_p, repeat, presence, frequency penalty), None when all neutral
         self.pen_n = 0               # penalty window length
+        self.lp_n = int(req.top_logprobs) if req.logprobs else -1  # alternatives per token; -1: no logprobs
+        self.lps: List[tuple] = []   # one entry per token of `out`
         self.p_off = 0               # incremental detokenization window [p_off, r_off) already emitted
         self.r_off = 0
 
@@ -123,6 +133,9 @@ class Scheduler:
                 raise ValueError(f"unknown sampling default {k!r}")
             self.sampling_defaults[k] = float(v)
         self._warned_no_processors = False
+        # per-token logprobs need the engine's set_logprobs / last_logprobs (a tensor-parallel tier has
+        # neither: its lm_head is vocab-parallel)
+        self.can_logprobs = hasattr(engine, "set_logprobs") and hasattr(engine, "last_logprobs")
         self.tok = tokenizer
         self.max_batch = max_batch
         self.max_ctx = max_ctx
@@ -270,6 +283,11 @@ class Scheduler:
         ids = r.prompt_ids
         if len(ids) >= self.max_ctx:
             raise ValueError(f"prompt of {len(ids)} tokens exceeds the context window ({self.max_ctx})")
+        if r.logprobs:
+            if not 0 <= int(r.top_logprobs) <= host_sampler.LOGPROB_MAX_TOP:
+                raise ValueError(f"top_logprobs outside 0..{host_sampler.LOGPROB_MAX_TOP}")
+            if not self.can_logprobs:
+                raise ValueError(f"{self.name}: this tier's engine cannot report logprobs")
         r.max_tokens = max(1, min(r.max_tokens, self.max_ctx - len(ids)))
         r.min_tokens = min(r.min_tokens, r.max_tokens)
         slot, common = self._pick_slot(ids)
@@ -324,21 +342,29 @@ class Scheduler:
         if hasattr(self.engine, "sample_first"):
             # on the device, the decode steps' sampler and RNG stream (seed, position)
             self._processors([seq])
+            self._stage_logprobs([seq])
             tok = int(self.engine.sample_first(seq.pos - 1, float(r.temperature), topk, topp, seq.seed,
                                                bytes(mask) if mask is not None else b""))
+            lp = self._read_logprobs([seq])[0]
         else:
             rng = np.random.default_rng([seq.seed & 0xFFFFFFFF, seq.pos - 1])
             min_p = 0.0
+            raw = logits
             if seq.proc is not None:
                 min_p = seq.proc[0]
                 logits = host_sampler.apply_penalties(logits, self._window(seq), *seq.proc[1:])
             tok = host_sampler.sample(logits, r.temperature, r.top_k, r.top_p, mask, rng, min_p=min_p)
+            lp = None
+            if seq.lp_n >= 0:  # (`raw`: the prefill's logits, before the penalties above)
+                x, ids, xs = host_sampler.logprobs(raw, tok, seq.lp_n)
+                lp = (x, list(zip(ids, xs)))
         seq.t_first = time.time()
         self.active.append(seq)
-        self._accept(seq, tok)
+        self._accept(seq, tok, lp)
 
-    def _accept(self, seq: _Seq, tok: int) -> bool:
-        """Record a sampled token; returns False when the sequence finished."""
+    def _accept(self, seq: _Seq, tok: int, lp=None) -> bool:
+        """Record a sampled token (lp: its logprob entry, kept only with a token that is emitted);
+        returns False when the sequence finished."""
         r = seq.req
         if r.cancelled:
             self._finish(seq, "cancelled")
@@ -351,6 +377,8 @@ class Scheduler:
                 self._finish(seq, "stop")
                 return False
         seq.out.append(tok)
+        if seq.lp_n >= 0:
+            seq.lps.append((int(tok), lp[0], lp[1]))
         seq.last = tok
         self.stats["tokens"] += 1
         self._tok_times.append(time.time())
@@ -432,10 +460,11 @@ class Scheduler:
     def _take(self, rows, out):
         self.stats["steps"] += 1
         self.stats["batch_sum"] += len(rows)
-        for s, t in zip(rows, out):
+        lps = self._read_logprobs(rows)
+        for s, t, lp in zip(rows, out, lps):
             s.pos += 1
             self.slot_cache[s.slot].append(s.last)
-            self._accept(s, int(t))
+            self._accept(s, int(t), lp)
 
     def _can_speculate(self, rows) -> bool:
         """Whether step t+1 of the same rows can be queued before step t's tokens are known: no
@@ -486,6 +515,30 @@ class Scheduler:
         setp(list(cols[0]), list(cols[1]), list(cols[2]), list(cols[3]),
              [self._window(s) if s.proc is not None else [] for s in rows])
 
+    def _stage_logprobs(self, rows):
+        """Before a sampler launch, after _processors: the rows' top_logprobs for the engine's logprob
+        launch behind it.  No row asks: no call at all."""
+        if any(s.lp_n >= 0 for s in rows):
+            self.engine.set_logprobs([s.lp_n for s in rows])
+
+    def _read_logprobs(self, rows) -> list:
+        """After the rows' sampled tokens reached the host: one entry per row, (the token's logprob,
+        [(alternative id, logprob), ...]) or None for a row that did not ask."""
+        if not any(s.lp_n >= 0 for s in rows):
+            return [None] * len(rows)
+        got = self.engine.last_logprobs()
+        if len(got) != 3 or len(got[0]) != len(rows):
+            raise RuntimeError("the engine returned no logprobs for a step that staged them")
+        lp, ids, lps = got
+        out = []
+        for b, s in enumerate(rows):
+            if s.lp_n < 0:
+                out.append(None)
+                continue
+            top = [(int(i), float(x)) for i, x in zip(ids[b][:s.lp_n], lps[b][:s.lp_n]) if i >= 0]
+            out.append((float(lp[b]), top))
+        return out
+
     def _masks(self, rows) -> bytes:
         if not any(s.grammar_state is not None for s in rows):
             return b""
@@ -500,6 +553,7 @@ class Scheduler:
             rows = list(self.active)
             self._submit(rows, True)
             self._processors(rows)
+            self._stage_logprobs(rows)
             self.engine.decode_sample(self._masks(rows))
         self._pending = None
         spec = self._can_speculate(rows)
@@ -513,6 +567,7 @@ class Scheduler:
         if spec and self.active == rows:
             # nobody finished or joined: sample the queued forward with the masks of the new tokens
             self._processors(rows)
+            self._stage_logprobs(rows)
             self.engine.decode_sample(self._masks(rows))
             self._pending = rows
         # (spec and a row finished: the queued forward is dropped -- its KV writes at the next
@@ -541,16 +596,19 @@ class Scheduler:
                 self._full_mask = host_sampler.all_allowed(self.vocab)
             mask = b"".join(self._mask(s) if s.grammar_state is not None else self._full_mask for s in self.active)
         topp = [float(s.req.top_p) if 0.0 < s.req.top_p < 1.0 else 1.0 for s in self.active]
-        self._processors(self.active)
+        rows = list(self.active)
+        self._processors(rows)
+        self._stage_logprobs(rows)
         t1 = time.perf_counter()
         out = self.engine.decode(slots, toks, pos, temps, topk, 0, mask, topp, seeds)
         t2 = time.perf_counter()
         self.stats["steps"] += 1
         self.stats["batch_sum"] += B
-        for s, t in zip(list(self.active), out):
+        lps = self._read_logprobs(rows)
+        for s, t, lp in zip(rows, out, lps):
             s.pos += 1
             self.slot_cache[s.slot].append(s.last)
-            self._accept(s, int(t))
+            self._accept(s, int(t), lp)
         t3 = time.perf_counter()
         tm = self.timing
         tm["mask_s"] += t1 - t0
@@ -574,7 +632,8 @@ class Scheduler:
         self._done(r, GenResult(
             text=text, token_ids=list(seq.out), prompt_tokens=len(r.prompt_ids), completion_tokens=len(seq.out),
             finish_reason=reason, ttft_ms=(seq.t_first - r.submitted_at) * 1e3 if seq.t_first else 0.0,
-            latency_ms=(now - r.submitted_at) * 1e3, cached_prompt_tokens=seq.cached, error=error))
+            latency_ms=(now - r.submitted_at) * 1e3, cached_prompt_tokens=seq.cached, error=error,
+            logprobs=list(seq.lps) if seq.lp_n >= 0 else None))
 
     @staticmethod
     def _done(r: GenRequest, res: GenResult):

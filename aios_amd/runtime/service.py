@@ -24,6 +24,7 @@ import grpc
 from ..rpc.schema import pb
 from .chat_template import build_messages
 from .model_manager import ModelManager, RoutingError
+from .sampler import LOGPROB_MAX_TOP
 from .scheduler import GenRequest, GenResult
 
 log = logging.getLogger("aios.runtime.service")
@@ -60,9 +61,52 @@ def sampling_from_body(body: dict) -> dict:
     return {k: cast(body[k]) for k, cast in SAMPLING_FIELDS.items() if body.get(k) is not None}
 
 
+LOGPROB_NEG_INF = -9999.0  # -inf is not valid JSON; OpenAI reports it as -9999.0
+
+
+def logprobs_from_body(body: dict, scheduler) -> Optional[int]:
+    """`logprobs` / `top_logprobs` of a /v1/chat/completions body: None (not asked) or the number of
+    alternatives per token; ValueError (-> 400) for what OpenAI rejects and what this runtime cannot serve"""
+    want, top = body.get("logprobs"), body.get("top_logprobs")
+    if want is not None and not isinstance(want, bool):
+        raise ValueError("logprobs must be a boolean")
+    if top is not None:
+        if not want:
+            raise ValueError("top_logprobs requires logprobs: true")
+        if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= LOGPROB_MAX_TOP:
+            raise ValueError(f"top_logprobs must be an integer in 0..{LOGPROB_MAX_TOP}")
+    if not want:
+        return None
+    if body.get("stream"):
+        raise ValueError("logprobs are not available with stream: true")
+    if not getattr(scheduler, "can_logprobs", False):  # (a tensor-parallel tier: vocab-parallel lm_head)
+        raise ValueError("this model's engine cannot report logprobs")
+    return int(top or 0)
+
+
+def logprobs_content(tokenizer, entries) -> list:
+    """GenResult.logprobs as OpenAI's choices[0].logprobs.content: per token its piece (`bytes`: the
+    piece's raw bytes, `token`: their UTF-8 decoding, U+FFFD where the piece alone is not valid UTF-8),
+    its logprob and the alternatives, best first"""
+    def item(tid, lp):
+        raw = tokenizer.token_bytes(int(tid))
+        finite = lp == lp and lp not in (float("inf"), float("-inf"))
+        return {"token": raw.decode("utf-8", errors="replace"), "logprob": float(lp) if finite else LOGPROB_NEG_INF,
+                "bytes": list(raw)}
+
+    out = []
+    for tid, lp, top in entries or []:
+        it = item(tid, lp)
+        it["top_logprobs"] = [item(i, x) for i, x in top]
+        out.append(it)
+    return out
+
+
 async def generate(m, messages, max_tokens: int, temperature: float, json_mode: bool, on_delta=None,
-                   timeout: float = 120.0, seed: int = 0, sampling: Optional[dict] = None) -> GenResult:
-    """sampling: further GenRequest fields by name (top_p, top_k, seed, min_p, the penalties)"""
+                   timeout: float = 120.0, seed: int = 0, sampling: Optional[dict] = None,
+                   top_logprobs: Optional[int] = None) -> GenResult:
+    """sampling: further GenRequest fields by name (top_p, top_k, seed, min_p, the penalties);
+    top_logprobs: None, or per-token logprobs with that many alternatives (GenResult.logprobs)"""
     loop = asyncio.get_running_loop()
     fut = loop.create_future()
     prompt = m.template.render(messages, add_generation_prompt=True)
@@ -81,6 +125,8 @@ async def generate(m, messages, max_tokens: int, temperature: float, json_mode: 
         if k not in SAMPLING_FIELDS:
             raise ValueError(f"unknown sampling field {k!r}")
         setattr(req, k, v)
+    if top_logprobs is not None:
+        req.logprobs, req.top_logprobs = True, int(top_logprobs)
     m.scheduler.submit(req)
     try:
         return await asyncio.wait_for(fut, timeout + 5)
@@ -252,6 +298,10 @@ class AIRuntimeService:
         except (TypeError, ValueError) as e:
             return web.json_response({"error": {"message": f"bad sampling field: {e}", "type": "invalid_request_error"}},
                                      status=400)
+        try:
+            top_logprobs = logprobs_from_body(body, m.scheduler)
+        except ValueError as e:
+            return web.json_response({"error": {"message": str(e), "type": "invalid_request_error"}}, status=400)
         created = int(time.time())
         rid = f"chatcmpl-{created}{id(request) & 0xffff:04x}"
         if body.get("stream"):
@@ -274,11 +324,15 @@ class AIRuntimeService:
             await resp.write(f"data: {json.dumps(end)}\n\ndata: [DONE]\n\n".encode())
             await resp.write_eof()
             return resp
-        res = await generate(m, messages, max_tokens, temperature, json_mode, sampling=sampling)
+        res = await generate(m, messages, max_tokens, temperature, json_mode, sampling=sampling,
+                             top_logprobs=top_logprobs)
+        choice = {"index": 0, "message": {"role": "assistant", "content": res.text},
+                  "finish_reason": "length" if res.finish_reason == "length" else "stop"}
+        if top_logprobs is not None:  # (bodies of requests that did not ask stay as they were)
+            choice["logprobs"] = {"content": logprobs_content(m.tokenizer, res.logprobs)}
         return web.json_response({
             "id": rid, "object": "chat.completion", "created": created, "model": m.name,
-            "choices": [{"index": 0, "message": {"role": "assistant", "content": res.text},
-                         "finish_reason": "length" if res.finish_reason == "length" else "stop"}],
+            "choices": [choice],
             "usage": {"prompt_tokens": res.prompt_tokens, "completion_tokens": res.completion_tokens,
                       "total_tokens": res.prompt_tokens + res.completion_tokens},
             "timings": {"ttft_ms": res.ttft_ms, "latency_ms": res.latency_ms,

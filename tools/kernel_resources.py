@@ -33,6 +33,7 @@ HOT = [
     "aios::gemm_skinny_kernel<*",
     "aios::gemm_ring_kernel<*",
     "aios::sample_kernel*",
+    "aios::logprob_kernel*",
     "aios::get_rows_step_kernel*",
 ]
 
