@@ -232,6 +232,22 @@ PYBIND11_MODULE(_engine, m) {
              return py::array_t<float>(out.size(), out.data());
            },
            py::arg("slot"), py::arg("tokens"), py::arg("start_pos") = 0, py::arg("want_logits") = true)
+      .def("embed_prefill",
+           [](Engine& e, int slot, const std::vector<int>& tokens, int start_pos, int pooling, bool final) -> py::object {
+             // final: the [d] unit vector, or for pooling 0 (none) the [tokens][d] normed rows; else an empty array
+             std::vector<float> out;
+             {
+               py::gil_scoped_release nogil;
+               out = e.embed_prefill(slot, tokens, start_pos, pooling, final);
+             }
+             py::array_t<float> a(out.size(), out.data());
+             if (final && pooling == EMBED_NONE)
+               return a.reshape({(py::ssize_t)e.embed_tokens(), (py::ssize_t)e.config().d_model});
+             return a;
+           },
+           py::arg("slot"), py::arg("tokens"), py::arg("start_pos") = 0, py::arg("pooling") = (int)EMBED_MEAN,
+           py::arg("final") = true)
+      .def("embed_tokens", &Engine::embed_tokens)
       .def("decode",
            [](Engine& e, const std::vector<int>& slots, const std::vector<int>& tokens, const std::vector<int>& pos,
               const std::vector<float>& temperature, const std::vector<int>& top_k, uint64_t seed, py::bytes mask,
@@ -759,6 +775,26 @@ PYBIND11_MODULE(_engine, m) {
         },
         py::arg("logits"), py::arg("ldl"), py::arg("B"), py::arg("V"), py::arg("tokens"), py::arg("top_n"),
         py::arg("out_lp"), py::arg("out_id"), py::arg("st"));
+  m.attr("EMBED_NONE") = (int)EMBED_NONE;
+  m.attr("EMBED_MEAN") = (int)EMBED_MEAN;
+  m.attr("EMBED_LAST") = (int)EMBED_LAST;
+  m.attr("EMBED_MAX_D") = EMBED_MAX_D;
+  m.attr("EMBED_MAX_WG") = EMBED_MAX_WG;
+  m.def("embed_pool_ws_bytes", &embed_pool_ws_bytes);
+  m.def("embed_pool",
+        [](uintptr_t x, int ldx, int n, int d, uintptr_t g, float eps, uintptr_t acc, uintptr_t count, int mode, int first,
+           int final, uintptr_t out, uintptr_t ws, size_t ws_bytes, uintptr_t counter, uintptr_t st) {
+          // every buffer is the caller's: ws of embed_pool_ws_bytes(d) bytes, counter one zeroed int
+          EmbedPoolArgs a;
+          std::memset(&a, 0, sizeof(a));
+          a.x = (const float*)x; a.ldx = ldx; a.n = n; a.d = d; a.g = (const float*)g; a.eps = eps;
+          a.acc = (float*)acc; a.count = (int*)count; a.mode = mode; a.first = first; a.final = final;
+          a.out = (float*)out; a.ws = (float*)ws; a.ws_bytes = ws_bytes; a.counter = (int*)counter;
+          launch_embed_pool(a, S(st));
+        },
+        py::arg("x"), py::arg("ldx"), py::arg("n"), py::arg("d"), py::arg("g"), py::arg("eps"), py::arg("acc"),
+        py::arg("count"), py::arg("mode"), py::arg("first"), py::arg("final"), py::arg("out"), py::arg("ws"),
+        py::arg("ws_bytes"), py::arg("counter"), py::arg("st"));
   m.def("gemm",
         [](uintptr_t A, int lda, PyQMatrix* w, int M, uintptr_t C, int ldc, int accumulate, uintptr_t st) {
           GemmArgs a;

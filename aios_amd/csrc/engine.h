@@ -111,6 +111,23 @@ class Engine {
   // Prefill `tokens` into `slot` starting at position `start_pos`.  Returns logits of the last
   // token (host copy) if want_logits, and leaves the slot ready to decode.
   std::vector<float> prefill(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits);
+  // Text embedding of a prompt (ops.h EmbedPoolArgs: the rule).  Runs the forward and KV writes of
+  // prefill(slot, tokens, start_pos, false) -- the slot afterwards holds valid KV for those positions --
+  // and after each internal chunk folds that chunk's hidden rows into the slot's pooling state.  One
+  // difference from prefill: chunks that reach the prefill GEMM (more than 32 rows) ask for its best plan
+  // without split-K / stream-K (GemmQArgs::ksplit < 0), whose fp32 atomics make two prefills of one prompt
+  // differ in the low bits.  With that, calls of 5 tokens or more give the same bytes every time; shorter
+  // ones take the GEMV path, whose bf16 kernels sum with LDS float atomics, and may differ in the last bits.
+  // A prompt
+  // may come in several calls (the scheduler's chunked prefill): start_pos == 0 resets the slot's state, a
+  // later call must start where the last one ended, with the same pooling (else it throws: a chunk was
+  // skipped or repeated); EMBED_LAST keeps no state and may start anywhere (a cached prefix).  EMBED_NONE
+  // stages its rows in ONE device buffer (max_ctx x d floats, allocated by the first such call): a NONE call
+  // on another slot ends the prompt being staged, whose next call then throws.  final ==
+  // false returns nothing; final == true returns the d floats of the unit vector, or for EMBED_NONE the
+  // (start_pos + T) x d normed rows, staged on the device and copied out once.  Single-GPU engines only.
+  std::vector<float> embed_prefill(int slot, const std::vector<int>& tokens, int start_pos, int pooling, bool final);
+  int embed_tokens() const { return emb_tokens_; }  // tokens pooled by the last final embed_prefill
   // One decode step for B sequences: input token ids at positions pos[b] in slots[b].  Samples
   // with per-row temperature/top_k (0 = greedy) and optional grammar bitmasks; returns tokens.
   std::vector<int> decode(const std::vector<int>& slots, const std::vector<int>& tokens, const std::vector<int>& pos,
@@ -288,7 +305,29 @@ class Engine {
   uint8_t* h_mask_ = nullptr;            // pinned staging of the pipelined sampler's masks
   hipEvent_t pipe_ev_ = nullptr;         // the pipelined sampler's token copy
   bool gemm_prefill_ok(int T) const;
-  void prefill_gemm(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits);
+  // embed_prefill's hook into the prefill: what to do with each chunk's hidden rows (null: plain prefill,
+  // nothing is enqueued for it)
+  struct EmbedFold {
+    int slot, pooling;
+    bool final;
+  };
+  // prefill()'s body; fold: each chunk's rows also go through embed_fold
+  std::vector<float> prefill_run(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
+                                 const EmbedFold* fold);
+  void prefill_gemm(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
+                    const EmbedFold* fold = nullptr);
+  // n hidden rows x[n][d] of positions [pos0, pos0 + n) of f.slot; last: the call's last chunk
+  void embed_fold(const EmbedFold& f, const float* x, int n, int pos0, bool last);
+  void embed_buffers(bool rows);           // allocated by the first embed_prefill (rows: by the first EMBED_NONE)
+  float* emb_acc_ = nullptr;               // [max_slots][d] running sums of x / rms
+  int* emb_count_ = nullptr;               // [max_slots] rows folded (device; the kernel's count)
+  float* emb_out_ = nullptr;               // [d] the unit vector of a final call
+  float* emb_rows_ = nullptr;              // [max_ctx][d] EMBED_NONE's staged rows, one buffer for every slot
+  int emb_rows_slot_ = -1;                 // the slot whose rows it holds
+  float* emb_ws_ = nullptr;                // embed_pool_ws_bytes(d)
+  int* emb_cnt_ = nullptr;                 // the pool kernel's ticket
+  std::vector<int> emb_pos_, emb_mode_;    // [max_slots] position reached (-1: no state) and its pooling
+  int emb_tokens_ = 0;
   void layer_decode(int l, int B);
   void gemv(const std::vector<const QMat*>& segs, int N, int K, int B, const float* x, int ldx, const float* norm_w,
             float* y, int ldy, int epi, int layer);

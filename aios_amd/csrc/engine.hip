@@ -1315,7 +1315,8 @@ bool Engine::gemm_prefill_ok(int T) const { return gm_ok_ && T >= gm_min_rows_; 
 //   gate/up GEMM with the SwiGLU epilogue -> bf16 | down GEMM (+= residual)
 // so every weight byte is dequantised once per chunk (not once per 8 rows as on the GEMV path).
 // TP: the row-parallel O / down outputs go through the all-reduce hook into the residual.
-void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits) {
+void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
+                          const EmbedFold* fold) {
   TraceRange tr("aios.prefill_gemm");
   const int T = (int)tokens.size();
   const int d = cfg_.d_model, hd = cfg_.head_dim, H = cfg_.n_heads, Hkv = cfg_.n_kv_heads, ff = cfg_.d_ff;
@@ -1332,6 +1333,15 @@ void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_po
     // GEMM, kernels/gemm_pf.hip, with the plain epilogues)
     const bool sh = short_fuse && !tp && n <= 32;
     const bool fnp = sh && gm_nparts_ > 0;
+    // The prefill GEMM's split-K and stream-K plans add their partial tiles with fp32 atomics, in arrival
+    // order, so two prefills of one prompt differ in the low bits (up to 9e-05 on the pooled unit vector
+    // of a bf16 model).  An embedding's chunks that reach it (more than 32 rows) ask for its best plan
+    // without them (ksplit < 0), so the same tokens pool to the same bytes; prefill() keeps its plans.
+    const bool no_split = fold && n > 32;
+    auto run = [&](GemmQArgs& g) {
+      if (no_split) g.ksplit = -1;
+      gemm(g);
+    };
     for (int i = 0; i < n; ++i) hp[i] = start_pos + r0 + i;
     HIP_CHECK(hipMemcpyAsync(gm_tokens_, tokens.data() + r0, n * 4, hipMemcpyHostToDevice, stream_));
     HIP_CHECK(hipMemcpyAsync(gm_pos_, hp.data(), n * 4, hipMemcpyHostToDevice, stream_));
@@ -1376,7 +1386,7 @@ void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_po
         qepi = sh || (pf_qkv && gemm_pf_serves(q));
         if (qepi) g = q;
       }
-      gemm(g);
+      run(g);
       if (!qepi) {
       QkvPostArgs p;
       p.qkv = gm_qkv_; p.ldqkv = ldqkv; p.T = n;
@@ -1402,7 +1412,7 @@ void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_po
       g.A = gm_attn16_; g.lda = qd; g.M = n; g.K = qd; g.nseg = 1; g.seg[0] = L.wo.w; g.N = d; g.ldc = d;
       if (tp) { g.C = gm_part_; g.epi = GEPI_STORE; } else { g.C = gm_x_; g.epi = GEPI_ACCUM; }
       if (fnp) nrm_out(g, L.ffn_norm);
-      gemm(g);
+      run(g);
       if (tp) allreduce(gm_part_, (size_t)n * d, gm_x_);
       // FFN
       if (!fnp) launch_rmsnorm_bf16(gm_x_, d, L.ffn_norm, gm_a16_, d, n, d, cfg_.norm_eps, stream_);
@@ -1410,19 +1420,25 @@ void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_po
       g.A = gm_a16_; g.lda = d; g.M = n; g.K = d; g.nseg = 1; g.seg[0] = L.wgu.w; g.N = 2 * ff;
       g.C16 = gm_ff16_; g.ldc = ff; g.epi = GEPI_SWIGLU_BF16;
       if (fnp) nrm_in(g);
-      gemm(g);
+      run(g);
       std::memset(&g, 0, sizeof(g));
       g.A = gm_ff16_; g.lda = ff; g.M = n; g.K = ff; g.nseg = 1; g.seg[0] = L.wdown.w; g.N = d; g.ldc = d;
       if (tp) { g.C = gm_part_; g.epi = GEPI_STORE; } else { g.C = gm_x_; g.epi = GEPI_ACCUM; }
       if (fnp && l + 1 < cfg_.n_layers) nrm_out(g, layers_[l + 1].attn_norm);  // (lm_head normalises its row)
-      gemm(g);
+      run(g);
       if (tp) allreduce(gm_part_, (size_t)n * d, gm_x_);
     }
     if (r0 + n == T && want_logits) lm_head(1, gm_x_ + (size_t)(n - 1) * d, d);
+    if (fold) embed_fold(*fold, gm_x_, n, start_pos + r0, r0 + n == T);
   }
 }
 
 std::vector<float> Engine::prefill(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits) {
+  return prefill_run(slot, tokens, start_pos, want_logits, nullptr);
+}
+
+std::vector<float> Engine::prefill_run(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
+                                       const EmbedFold* fold) {
   const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
   TraceRange tr("aios.prefill");
   if (!finalized_) throw std::runtime_error("engine not finalized");
@@ -1436,7 +1452,7 @@ std::vector<float> Engine::prefill(int slot, const std::vector<int>& tokens, int
   kv_prepare_write(slot, start_pos, start_pos + T);
   kv_sync(0);
   if (gemm_prefill_ok(T)) {
-    prefill_gemm(slot, tokens, start_pos, want_logits);
+    prefill_gemm(slot, tokens, start_pos, want_logits, fold);
     std::vector<float> out;
     if (want_logits) {
       out.resize(cfg_.vocab_size);
@@ -1573,6 +1589,7 @@ std::vector<float> Engine::prefill(int slot, const std::vector<int>& tokens, int
       }
       x_ = xb; q_ = qb; qkv_ = qkvb; attn_ = ab; ff_ = fb;
       if (r0 + n == T && want_logits) lm_head(1, x_ + (size_t)(n - 1) * d, d);
+      if (fold) embed_fold(*fold, x_, n, start_pos + r0, r0 + n == T);
     }
   } catch (...) {
     std::swap(x_, pf_x_); std::swap(q_, pf_q_); std::swap(qkv_, pf_qkv_); std::swap(attn_, pf_attn_);
@@ -1588,6 +1605,81 @@ std::vector<float> Engine::prefill(int slot, const std::vector<int>& tokens, int
     out.resize(V);
     HIP_CHECK(hipMemcpyAsync(out.data(), logits_, (size_t)V * 4, hipMemcpyDeviceToHost, stream_));
   }
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  return out;
+}
+
+// ---- text embeddings (engine.h embed_prefill) -----------------------------------------------------
+void Engine::embed_buffers(bool rows) {
+  // First use, not finalize: an engine that never embeds allocates what it always did.  All or nothing:
+  // the members are set only once every allocation of a group succeeded (a failed dmalloc throws; what it
+  // got before stays in allocs_ and is freed with the engine).
+  const size_t d = cfg_.d_model;
+  if (!emb_acc_) {
+    float* acc = (float*)dmalloc((size_t)cfg_.max_slots * d * 4);
+    float* out = (float*)dmalloc(d * 4);
+    float* ws = (float*)dmalloc(embed_pool_ws_bytes((int)d));
+    int* count = (int*)dmalloc((size_t)cfg_.max_slots * 4);
+    int* cnt = (int*)dmalloc(4);
+    HIP_CHECK(hipMemset(count, 0, (size_t)cfg_.max_slots * 4));
+    HIP_CHECK(hipMemset(cnt, 0, 4));
+    HIP_CHECK(hipStreamSynchronize(nullptr));  // (the memsets ran on the null stream, the kernel runs on ours)
+    emb_pos_.assign(cfg_.max_slots, -1);
+    emb_mode_.assign(cfg_.max_slots, -1);
+    emb_out_ = out; emb_ws_ = ws; emb_count_ = count; emb_cnt_ = cnt;
+    emb_acc_ = acc;
+    ws_bytes_ += ((size_t)cfg_.max_slots * d + d) * 4 + embed_pool_ws_bytes((int)d) + (size_t)cfg_.max_slots * 4 + 4;
+  }
+  if (rows && !emb_rows_) {  // max_ctx x d floats, by the first EMBED_NONE call only
+    emb_rows_ = (float*)dmalloc((size_t)cfg_.max_ctx * d * 4);
+    ws_bytes_ += (size_t)cfg_.max_ctx * d * 4;
+  }
+}
+
+void Engine::embed_fold(const EmbedFold& f, const float* x, int n, int pos0, bool last) {
+  if (f.pooling == EMBED_LAST && !(f.final && last)) return;  // only the prompt's last row counts
+  EmbedPoolArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.x = x; a.ldx = cfg_.d_model; a.n = n; a.d = cfg_.d_model;
+  a.g = out_norm_; a.eps = cfg_.norm_eps;
+  a.acc = emb_acc_ + (size_t)f.slot * cfg_.d_model; a.count = emb_count_ + f.slot;
+  a.mode = f.pooling; a.first = pos0 == 0; a.final = f.final && last;
+  a.out = f.pooling == EMBED_NONE ? emb_rows_ + (size_t)pos0 * cfg_.d_model : emb_out_;
+  a.ws = emb_ws_; a.ws_bytes = embed_pool_ws_bytes(cfg_.d_model); a.counter = emb_cnt_;
+  launch_embed_pool(a, stream_);
+}
+
+std::vector<float> Engine::embed_prefill(int slot, const std::vector<int>& tokens, int start_pos, int pooling,
+                                         bool final) {
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  if (cfg_.tp_size > 1) throw std::runtime_error("embeddings: single-GPU engines only");
+  if (pooling != EMBED_NONE && pooling != EMBED_MEAN && pooling != EMBED_LAST)
+    throw std::runtime_error("embed_prefill: pooling must be 0 (none), 1 (mean) or 3 (last)");
+  if (slot < 0 || slot >= cfg_.max_slots) throw std::runtime_error("embed_prefill: bad slot");
+  if (start_pos < 0) throw std::runtime_error("embed_prefill: bad start_pos");
+  const int d = cfg_.d_model, T = (int)tokens.size();
+  if (d % 64 || d > EMBED_MAX_D) throw std::runtime_error("embeddings: d_model must be a multiple of 64 up to 8192");
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  embed_buffers(pooling == EMBED_NONE);
+  if (pooling != EMBED_LAST && start_pos != 0 && (emb_pos_[slot] != start_pos || emb_mode_[slot] != pooling))
+    throw std::runtime_error("embed_prefill: start_pos " + std::to_string(start_pos) + " does not continue the slot's " +
+                             "pooled positions (" + std::to_string(emb_pos_[slot]) + ")");
+  if (pooling == EMBED_NONE) {
+    // one staging buffer for every slot: a NONE call on another slot overwrites its first rows, so the
+    // prompt that was being staged there cannot be continued any more
+    if (emb_rows_slot_ >= 0 && emb_rows_slot_ != slot && emb_mode_[emb_rows_slot_] == EMBED_NONE) emb_pos_[emb_rows_slot_] = -1;
+    emb_rows_slot_ = slot;
+  }
+  emb_pos_[slot] = -1;  // (a call that throws leaves no state to continue)
+  const EmbedFold fold{slot, pooling, final};
+  prefill_run(slot, tokens, start_pos, false, &fold);
+  emb_pos_[slot] = start_pos + T;
+  emb_mode_[slot] = pooling;
+  if (!final) return {};
+  emb_tokens_ = start_pos + T;
+  std::vector<float> out(pooling == EMBED_NONE ? (size_t)emb_tokens_ * d : (size_t)d);
+  HIP_CHECK(hipMemcpyAsync(out.data(), pooling == EMBED_NONE ? emb_rows_ : emb_out_, out.size() * 4,
+                           hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
   return out;
 }

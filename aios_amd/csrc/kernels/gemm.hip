@@ -188,6 +188,7 @@ static void launch_big_tiles(const GemmQArgs& a, hipStream_t st) {
   const int cus = device_cu_count();
   // split-K only when the tile grid leaves most CUs idle (short prefill chunks)
   int S = a.ksplit;
+  if (S < 0) S = 1;  // (no split partials wanted: ops.h GemmQArgs::ksplit)
   if (S <= 0) {
     const int per_cu = std::max(1, 163840 / ((BM + BN) * 256));  // LDS-resident workgroups per CU
     S = tiles >= cus * per_cu / 2 ? 1 : std::max(1, std::min(a.K / 64 / 8, (cus * per_cu) / tiles));

@@ -236,6 +236,41 @@ struct LogprobArgs {
 void launch_logprobs(const LogprobArgs& a, hipStream_t st);
 size_t logprob_ws_bytes(int B, int V);
 
+// ---- text embeddings ---------------------------------------------------------------------------
+// Pooled embedding of hidden rows x[t] (the residual stream before output_norm), llama.cpp's --embedding
+// rule for a causal model:  h[t] = x[t] * g * rsqrt(mean(x[t]^2) + eps)  (the model's final RMSNorm);
+//   EMBED_MEAN: p = (1 / T) sum_t h[t];  EMBED_LAST: p = h[T - 1];  result p / ||p||_2, a p that is exactly
+//   zero giving the zero vector;  EMBED_NONE: the rows h[t] themselves, not L2-normalised.
+// One launch folds a chunk of n rows into the running state of one sequence: acc[d] = sum of x[t] / rms[t]
+// (g is applied once, at the end) and count = rows folded.  `first` zeroes both before folding; `final`
+// also writes the unit vector to out[d].  EMBED_LAST folds only the chunk's last row (as first);
+// EMBED_NONE touches no state and writes h for the chunk's rows to out[n][d].  Fixed summation order, no
+// float atomics: bit-identical from run to run; a sum split over several launches differs from the single
+// launch by fp32 rounding only.  kernels/embed_pool.hip; tests/embed_oracle.py is this rule in float64.
+// The codes are GGUF's {arch}.pooling_type.
+enum EmbedPooling { EMBED_NONE = 0, EMBED_MEAN = 1, EMBED_LAST = 3 };
+constexpr int EMBED_MAX_D = 8192;     // widest row (a multiple of 64 from 64 up)
+constexpr int EMBED_MAX_ROWS = 2048;  // most rows per launch (the prefill chunk)
+constexpr int EMBED_MAX_WG = 64;      // workgroups per launch = slabs of the workspace
+struct EmbedPoolArgs {
+  const float* x;  // [n][ldx]
+  int ldx;
+  int n, d;
+  const float* g;  // [d] output_norm weight
+  float eps;
+  float* acc;      // [d] in/out
+  int* count;      // [1] in/out
+  int mode;        // EmbedPooling
+  int first, final;
+  float* out;      // mean / last: [d], written when final; none: [n][d]
+  float* ws;       // embed_pool_ws_bytes(d): one [d] slab per workgroup
+  size_t ws_bytes;
+  int* counter;    // [1] arrival ticket, zero-initialised, self re-arming
+  int band = 0;    // rows per workgroup (set by the launcher)
+};
+void launch_embed_pool(const EmbedPoolArgs& a, hipStream_t st);
+size_t embed_pool_ws_bytes(int d);
+
 // ---- MFMA GEMM (prefill) ----------------------------------------------------------------------
 // C[M][N] (fp32, epilogue) = A[M][K] (bf16) x W[N][K]^T (quantized, dequantized tile-wise in LDS)
 struct GemmArgs {
@@ -267,7 +302,9 @@ struct GemmQArgs {
   bf16_t* C16;       // [M][ldc] bf16 (SWIGLU_BF16: column n/2 = silu(col n) * col n+1)
   int ldc;
   int epi;
-  int ksplit;        // K split over workgroups: 0 = auto, 1 = off
+  int ksplit;        // K split over workgroups: 0 = auto, 1 = off, < 0 = auto among the plans whose sums are
+                     // reproducible (no fp32-atomic split-K / stream-K partials: the prefill GEMM's tuned
+                     // S = 1 plan; the ring and skinny GEMMs' slab splits already are)
   // skinny (M <= 64) split-K: fp32 partial slabs [S][tiles][16*Mt][rows] + per-tile arrival
   // tickets (zero-initialised, re-armed by each tile's last arriver).  Null -> no split.
   float* ws;

@@ -44,6 +44,8 @@ class ModelConfig:
     eos_id: int = 2
     tokenizer_model: str = "llama"  # "llama" (SPM) or "gpt2" (byte-level BPE)
     chat_template: str = "zephyr"
+    # /v1/embeddings' default pooling, "mean" | "last": the GGUF's {arch}.pooling_type when it names one of them
+    pooling: str = "mean"
 
     @property
     def q_dim(self) -> int:
@@ -98,6 +100,8 @@ class ModelConfig:
             eos_id=int(reader.get("tokenizer.ggml.eos_token_id", 2)),
             tokenizer_model=str(reader.get("tokenizer.ggml.model", "llama")),
             chat_template=tmpl if isinstance(tmpl, str) else "zephyr",
+            # (llama.cpp's codes: 0 none, 1 mean, 2 cls, 3 last, 4 rank; only mean and last are served)
+            pooling={1: "mean", 3: "last"}.get(int(g("pooling_type", 1)), "mean"),
         )
 
 

@@ -96,6 +96,14 @@ class ReferenceModel:
     @torch.no_grad()
     def forward(self, tokens: List[int], cache: Optional[dict] = None) -> torch.Tensor:
         """Logits [T, V] for `tokens` appended after `cache` (created if None)."""
+        x = self._rms(self.hidden(tokens, cache), self.w["output_norm.weight"])
+        return self._mm(x, "output.weight" if "output.weight" in self.w else "token_embd.weight")
+
+    @torch.no_grad()
+    def hidden(self, tokens: List[int], cache: Optional[dict] = None) -> torch.Tensor:
+        """The final hidden rows [T, d] of `tokens` appended after `cache` (created if None): the residual
+        stream after the last layer, before output_norm -- what the embedding pools (csrc/ops.h
+        EmbedPoolArgs)."""
         cfg = self.cfg
         if cache is None:
             cache = self.new_cache()
@@ -150,8 +158,7 @@ class ReferenceModel:
             u = self._mm(h, p + "ffn_up.weight")
             x = x + self._mm(torch.nn.functional.silu(g) * u, p + "ffn_down.weight")
         cache["len"] = start + T
-        x = self._rms(x, self.w["output_norm.weight"])
-        return self._mm(x, "output.weight" if "output.weight" in self.w else "token_embd.weight")
+        return x
 
     @torch.no_grad()
     def greedy(self, prompt: List[int], n_new: int) -> List[int]:

@@ -340,6 +340,11 @@ class TPEngine:
             # sharded; the shard's own Engine.set_logprobs throws): the scheduler sees no such method,
             # refuses the request alone, and the HTTP endpoint answers 400
             raise AttributeError(name)
+        if name in ("embed_prefill", "embed_tokens"):
+            # no embeddings on a tensor-parallel tier (the shard's Engine.embed_prefill throws "single-GPU
+            # engines only"; the hidden state is replicated, so this is scope, not design): hidden like the
+            # logprob calls, so the scheduler fails that request alone and /v1/embeddings answers 400
+            raise AttributeError(name)
         attr = getattr(self._eng, name)
         if name not in self._FORWARD or not callable(attr):
             return attr

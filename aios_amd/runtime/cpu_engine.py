@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from ..models.reference import ReferenceModel
+from . import embedding as host_embedding
 from . import sampler as host_sampler
 
 
@@ -47,6 +48,8 @@ class CpuEngine:
         self._proc = None  # set_sample_processors: per-row processors of the next sampler call only
         self._lp = None    # set_logprobs: per-row top_n of the next sampler call only
         self._lp_out = ()  # last_logprobs: what the last sampler call reported
+        self._emb: Dict[int, dict] = {}  # embed_prefill: per-slot pooling state (pos, pooling, sum, rows)
+        self._emb_tokens = 0
 
     @classmethod
     def from_gguf(cls, path: str, max_ctx: int = 2048, max_slots: int = 4, max_batch: int = 4,
@@ -84,6 +87,48 @@ class CpuEngine:
         logits = self.model.forward(list(ids), c)[-1].numpy()
         self.last = logits[None]
         return logits if want_logits else []
+
+    def embed_prefill(self, slot: int, ids: List[int], start: int = 0, pooling: int = 1, final: bool = True):
+        """The native Engine's embed_prefill (runtime/embedding.py: the rule): prefill `ids` into the slot
+        and fold their final hidden rows into the slot's pooling state.  start == 0 resets it; a later call
+        must continue where the last one ended ("last" keeps no state and may start at a cached prefix).
+        final: the unit vector [d] (pooling 1 mean, 3 last) or the normed rows [tokens, d] (0 none); else an
+        empty array."""
+        pooling = host_embedding.pooling_code(pooling)
+        if not ids:
+            raise ValueError("embed_prefill: empty prompt")
+        if start + len(ids) > self.config.max_ctx:
+            raise ValueError("embed_prefill: context overflow")
+        st = self._emb.get(slot)
+        last = pooling == host_embedding.POOLING["last"]
+        if start == 0 or last:
+            st = dict(pos=start, pooling=pooling, sum=0.0, rows=[])
+        elif st is None or st["pos"] != start or st["pooling"] != pooling:
+            raise ValueError(f"embed_prefill: start_pos {start} does not continue the slot's pooled positions "
+                             f"({st['pos'] if st else -1})")
+        self._emb.pop(slot, None)  # (a call that throws leaves no state to continue)
+        c = self._cache_at(slot, start)
+        x = self.model.hidden(list(ids), c).double().cpu().numpy()
+        g = self.model.w["output_norm.weight"].double().cpu().numpy()
+        eps = self.cfg.norm_eps
+        if pooling == host_embedding.POOLING["none"]:
+            st["rows"].append(host_embedding.normed_rows(x, g, eps))
+        elif last:
+            st["sum"] = host_embedding.normed_rows(x[-1], g, eps)
+        else:  # the sum of x / rms; g is applied once at the end, as on the device
+            st["sum"] = st["sum"] + host_embedding.normed_rows(x, np.ones_like(g), eps).sum(0)
+        st["pos"] = start + len(ids)
+        self._emb[slot] = st
+        if not final:
+            return np.zeros(0, np.float32)
+        self._emb_tokens = st["pos"]
+        if pooling == host_embedding.POOLING["none"]:
+            return np.concatenate(st["rows"]).astype(np.float32)
+        p = st["sum"] if last else st["sum"] / st["pos"] * g
+        return host_embedding.unit(p).astype(np.float32)
+
+    def embed_tokens(self) -> int:
+        return self._emb_tokens
 
     def set_sample_processors(self, min_p, repeat_penalty, presence_penalty, frequency_penalty, recent):
         """Per-row min-p, penalties and penalty windows (the rows' recent token ids) for the NEXT

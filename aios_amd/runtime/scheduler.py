@@ -35,6 +35,7 @@ from typing import Callable, Deque, Dict, List, Optional
 
 import numpy as np
 
+from . import embedding as host_embedding
 from . import sampler as host_sampler
 
 log = logging.getLogger("aios.runtime.scheduler")
@@ -72,6 +73,11 @@ class GenRequest:
     # alternatives -- GenResult.logprobs.  The stream callback carries text only.
     logprobs: bool = False
     top_logprobs: int = 0
+    # text embedding instead of generation (runtime/embedding.py: the rule): "mean" | "last" | "none".  The
+    # prompt is prefilled like any other (admission, slot, chunks between decode steps) through the engine's
+    # embed_prefill and the request ends with it -- GenResult.embedding, finish_reason "embedding";
+    # max_tokens, json_mode, the sampling fields and logprobs are ignored
+    embed: Optional[str] = None
     stop_ids: Optional[List[int]] = None
     on_delta: Optional[Callable[[str], None]] = None
     on_done: Optional[Callable[["GenResult"], None]] = None
@@ -86,7 +92,7 @@ class GenResult:
     token_ids: List[int]
     prompt_tokens: int
     completion_tokens: int
-    finish_reason: str                # stop | length | grammar | cancelled | error | deadline
+    finish_reason: str                # stop | length | grammar | cancelled | error | deadline | embedding
     ttft_ms: float = 0.0
     latency_ms: float = 0.0
     cached_prompt_tokens: int = 0
@@ -94,11 +100,13 @@ class GenResult:
     # requests with logprobs=True: one (token id, logprob, [(alternative id, logprob), ...]) per entry of
     # token_ids, best alternative first; None otherwise
     logprobs: Optional[list] = None
+    # requests with embed set: the unit vector [d] ("mean", "last") or the normed rows [tokens, d] ("none")
+    embedding: Optional[np.ndarray] = None
 
 
 class _Seq:
     __slots__ = ("req", "slot", "pos", "last", "out", "grammar_state", "emitted", "t_first", "cached", "todo",
-                 "p_off", "r_off", "seed", "proc", "pen_n", "lp_n", "lps")
+                 "p_off", "r_off", "seed", "proc", "pen_n", "lp_n", "lps", "embedding")
 
     def __init__(self, req, slot):
         self.req, self.slot = req, slot
@@ -117,6 +125,7 @@ class _Seq:
         self.pen_n = 0               # penalty window length
         self.lp_n = int(req.top_logprobs) if req.logprobs else -1  # alternatives per token; -1: no logprobs
         self.lps: List[tuple] = []   # one entry per token of `out`
+        self.embedding = None        # an embedding request's result
         self.p_off = 0               # incremental detokenization window [p_off, r_off) already emitted
         self.r_off = 0
 
@@ -136,6 +145,8 @@ class Scheduler:
         # per-token logprobs need the engine's set_logprobs / last_logprobs (a tensor-parallel tier has
         # neither: its lm_head is vocab-parallel)
         self.can_logprobs = hasattr(engine, "set_logprobs") and hasattr(engine, "last_logprobs")
+        # text embeddings need the engine's embed_prefill (a tensor-parallel tier hides it)
+        self.can_embed = hasattr(engine, "embed_prefill")
         self.tok = tokenizer
         self.max_batch = max_batch
         self.max_ctx = max_ctx
@@ -160,7 +171,8 @@ class Scheduler:
         self.min_shared_prefix = int(os.environ.get("AIOS_MIN_SHARED_PREFIX", "128"))
         self.cv = threading.Condition()
         self.stop_flag = False
-        self.stats = dict(requests=0, tokens=0, prefill_tokens=0, cached_tokens=0, steps=0, batch_sum=0, errors=0)
+        self.stats = dict(requests=0, tokens=0, prefill_tokens=0, cached_tokens=0, steps=0, batch_sum=0, errors=0,
+                          embeddings=0)
         # health / metrics (ModelManager.supervise and HealthCheck details)
         self.max_slots = max_slots
         self.last_progress = time.time()   # last completed admission or decode step
@@ -279,7 +291,53 @@ class Scheduler:
                 return dst, src_len
         return best, best_len
 
+    def _admit_embedding(self, r: GenRequest):
+        """An embedding request: admitted like a prompt, prefilled by _prefill_chunk through embed_prefill."""
+        ids = r.prompt_ids
+        host_embedding.pooling_code(r.embed)  # (ValueError: unknown pooling)
+        if not self.can_embed:
+            raise ValueError(f"{self.name}: this tier's engine cannot compute embeddings")
+        if not ids:
+            raise ValueError("embedding input is empty")
+        if len(ids) > self.max_ctx:  # (no token is generated: the whole window may be prompt)
+            raise ValueError(f"prompt of {len(ids)} tokens exceeds the context window ({self.max_ctx})")
+        if r.embed == "none" and any(q.req.embed == "none" for q in self.prefilling):
+            # the engine stages "none" rows in one buffer for all slots: one such prompt at a time; this one
+            # waits at the head of the queue until the other's last chunk is through
+            with self.cv:
+                self.queue.appendleft(r)
+            return
+        if r.embed == "last":
+            slot, common = self._pick_slot(ids)  # a cached prefix serves: only the last row is pooled
+        else:  # cached positions have no hidden rows to pool: from position 0, in the least useful slot
+            slot, common = min(self.free_slots, key=lambda f: len(self.slot_cache[f])), 0
+        self.free_slots.remove(slot)
+        seq = _Seq(r, slot)
+        seq.lp_n = -1
+        self._begin_prefill(seq, common)
+
+    def _begin_prefill(self, seq: _Seq, common: int):
+        """An admitted sequence whose slot holds its first `common` prompt tokens: queue the rest for
+        prefill, and with nothing decoding (no stream to protect) prefill it right away."""
+        ids, slot = seq.req.prompt_ids, seq.slot
+        seq.cached = common
+        seq.pos = common
+        seq.todo = list(ids[common:])
+        self.slot_cache[slot] = list(ids[:common])
+        self.stats["cached_tokens"] += common
+        self.prefilling.append(seq)
+        if not self.active:
+            try:
+                self._prefill_chunk(seq, whole=True)
+            except Exception:
+                if seq in self.prefilling:  # the caller reports the error; the slot goes back
+                    self.prefilling.remove(seq)
+                    self.free_slots.append(slot)
+                raise
+
     def _admit(self, r: GenRequest):
+        if r.embed is not None:
+            return self._admit_embedding(r)
         ids = r.prompt_ids
         if len(ids) >= self.max_ctx:
             raise ValueError(f"prompt of {len(ids)} tokens exceeds the context window ({self.max_ctx})")
@@ -298,20 +356,7 @@ class Scheduler:
         if proc != tuple(NEUTRAL_PROCESSORS.values()):
             seq.proc = proc
             seq.pen_n = host_sampler.penalty_window(r.repeat_last_n)
-        seq.cached = common
-        seq.pos = common
-        seq.todo = list(ids[common:])
-        self.slot_cache[slot] = list(ids[:common])
-        self.stats["cached_tokens"] += common
-        self.prefilling.append(seq)
-        if not self.active:  # nothing decoding: no stream to protect, prefill it right away
-            try:
-                self._prefill_chunk(seq, whole=True)
-            except Exception:
-                if seq in self.prefilling:  # the caller reports the error; the slot goes back
-                    self.prefilling.remove(seq)
-                    self.free_slots.append(slot)
-                raise
+        self._begin_prefill(seq, common)
 
     def _prefill_chunk(self, seq: _Seq, whole: bool = False):
         """Prefill the next chunk of seq's prompt; the last chunk samples the first token and
@@ -323,7 +368,10 @@ class Scheduler:
         n = len(seq.todo) if (whole or not self.active) else min(len(seq.todo), max(1, self.prefill_chunk))
         chunk, last = seq.todo[:n], n == len(seq.todo)
         tp0 = time.perf_counter()
-        logits = self.engine.prefill(seq.slot, chunk, seq.pos, last)
+        if r.embed is not None:
+            emb = self.engine.embed_prefill(seq.slot, chunk, seq.pos, host_embedding.POOLING[r.embed], last)
+        else:
+            logits = self.engine.prefill(seq.slot, chunk, seq.pos, last)
         self.timing["prefill_s"] += time.perf_counter() - tp0
         self.step_log.append((time.perf_counter(), -n))  # a prefill chunk between decode steps
         seq.todo = seq.todo[n:]
@@ -331,6 +379,11 @@ class Scheduler:
         self.slot_cache[seq.slot].extend(chunk)
         self.stats["prefill_tokens"] += n
         if not last:
+            return
+        if r.embed is not None:  # the request ends here; the slot keeps the prompt's KV for a later chat
+            seq.embedding = np.asarray(emb, np.float32)
+            self.stats["embeddings"] += 1
+            self._finish(seq, "embedding")
             return
         self.prefilling.remove(seq)
         mask = None
@@ -633,7 +686,7 @@ class Scheduler:
             text=text, token_ids=list(seq.out), prompt_tokens=len(r.prompt_ids), completion_tokens=len(seq.out),
             finish_reason=reason, ttft_ms=(seq.t_first - r.submitted_at) * 1e3 if seq.t_first else 0.0,
             latency_ms=(now - r.submitted_at) * 1e3, cached_prompt_tokens=seq.cached, error=error,
-            logprobs=list(seq.lps) if seq.lp_n >= 0 else None))
+            logprobs=list(seq.lps) if seq.lp_n >= 0 else None, embedding=seq.embedding))
 
     @staticmethod
     def _done(r: GenRequest, res: GenResult):

@@ -17,12 +17,14 @@ import json
 import logging
 import os
 import time
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import grpc
+import numpy as np
 
 from ..rpc.schema import pb
 from .chat_template import build_messages
+from .embedding import MAX_INPUTS as MAX_EMBED_INPUTS
 from .model_manager import ModelManager, RoutingError
 from .sampler import LOGPROB_MAX_TOP
 from .scheduler import GenRequest, GenResult
@@ -100,6 +102,59 @@ def logprobs_content(tokenizer, entries) -> list:
         it["top_logprobs"] = [item(i, x) for i, x in top]
         out.append(it)
     return out
+
+
+def embedding_inputs(body: dict, tokenizer, max_ctx: int) -> List[List[int]]:
+    """The `input` of a /v1/embeddings body as token lists: a string, a list of strings, one tokenised input
+    (a list of ints) or a list of them.  Strings get BOS and no chat template.  ValueError: a 400."""
+    inp = body.get("input")
+
+    def is_id(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+
+    if isinstance(inp, str):
+        items = [inp]
+    elif isinstance(inp, list) and inp and all(is_id(v) for v in inp):
+        items = [inp]
+    elif isinstance(inp, list) and inp and all(isinstance(v, str) or (isinstance(v, list) and all(is_id(t) for t in v))
+                                                for v in inp):
+        items = inp
+    else:
+        raise ValueError("input must be a non-empty string, a list of strings, a list of token ids or a list of "
+                         "token-id lists")
+    if len(items) > MAX_EMBED_INPUTS:
+        raise ValueError(f"at most {MAX_EMBED_INPUTS} inputs per request, got {len(items)}")
+    out = []
+    for i, it in enumerate(items):
+        if len(it) == 0:
+            raise ValueError(f"input {i} is empty")
+        ids = tokenizer.encode(it, add_bos=True, parse_special=False) if isinstance(it, str) else [int(t) for t in it]
+        if any(not 0 <= t < tokenizer.vocab_size for t in ids):
+            raise ValueError(f"input {i}: token id outside [0, {tokenizer.vocab_size})")
+        if len(ids) > max_ctx:
+            raise ValueError(f"input {i}: {len(ids)} tokens exceed the context window ({max_ctx})")
+        out.append(ids)
+    return out
+
+
+async def embed(m, inputs: List[List[int]], pooling: str, timeout: float = 120.0) -> List[GenResult]:
+    """Submit the inputs to the model's scheduler together; their results in input order."""
+    loop = asyncio.get_running_loop()
+    futs, reqs = [], []
+    for ids in inputs:
+        fut = loop.create_future()
+        reqs.append(GenRequest(prompt_ids=ids, embed=pooling, deadline=time.time() + timeout,
+                               on_done=lambda res, fut=fut: loop.call_soon_threadsafe(
+                                   lambda: fut.done() or fut.set_result(res))))
+        futs.append(fut)
+    for r in reqs:
+        m.scheduler.submit(r)
+    try:
+        return list(await asyncio.wait_for(asyncio.gather(*futs), timeout + 5))
+    except asyncio.TimeoutError:
+        for r in reqs:
+            r.cancelled = True
+        raise
 
 
 async def generate(m, messages, max_tokens: int, temperature: float, json_mode: bool, on_delta=None,
@@ -263,6 +318,7 @@ class AIRuntimeService:
         app.router.add_get("/health", self._http_health)
         app.router.add_post("/v1/chat/completions", self._http_chat)
         app.router.add_get("/v1/models", self._http_models)
+        app.router.add_post("/v1/embeddings", self._http_embeddings)
         runner = web.AppRunner(app, access_log=None)
         await runner.setup()
         try:
@@ -338,6 +394,52 @@ class AIRuntimeService:
             "timings": {"ttft_ms": res.ttft_ms, "latency_ms": res.latency_ms,
                         "cached_prompt_tokens": res.cached_prompt_tokens},
         })
+
+    async def _http_embeddings(self, request):
+        """OpenAI's /v1/embeddings (runtime/embedding.py: the rule).  `pooling`: "mean" | "last", an extension;
+        its default is the model's (ModelConfig.pooling).  `dimensions` is refused."""
+        import base64
+
+        from aiohttp import web
+
+        m = request.app["model"]
+
+        def bad(msg):
+            return web.json_response({"error": {"message": msg, "type": "invalid_request_error"}}, status=400)
+
+        try:
+            body = await request.json()
+        except ValueError:
+            return bad("the body is not JSON")
+        if not isinstance(body, dict):
+            return bad("the body must be a JSON object")
+        if body.get("dimensions") is not None:
+            return bad("dimensions is not supported: this model is not trained for truncated embeddings")
+        fmt = body.get("encoding_format", "float")
+        if fmt not in ("float", "base64"):
+            return bad('encoding_format must be "float" or "base64"')
+        pooling = body.get("pooling", getattr(getattr(m, "config", None), "pooling", "mean"))
+        if pooling not in ("mean", "last"):
+            return bad('pooling must be "mean" or "last"')
+        if not getattr(m.scheduler, "can_embed", False):  # (a tensor-parallel tier)
+            return bad("this model's engine cannot compute embeddings (single-GPU tiers only)")
+        try:
+            inputs = embedding_inputs(body, m.tokenizer, m.scheduler.max_ctx)
+        except ValueError as e:
+            return bad(str(e))
+        results = await embed(m, inputs, pooling)
+        for res in results:
+            if res.finish_reason != "embedding":
+                return web.json_response({"error": {"message": res.error or res.finish_reason, "type": "server_error"}},
+                                         status=500)
+        data = []
+        for i, res in enumerate(results):
+            v = np.asarray(res.embedding, "<f4")
+            data.append({"object": "embedding", "index": i,
+                         "embedding": base64.b64encode(v.tobytes()).decode() if fmt == "base64" else v.tolist()})
+        n = sum(len(ids) for ids in inputs)
+        return web.json_response({"object": "list", "data": data, "model": m.name,
+                                  "usage": {"prompt_tokens": n, "total_tokens": n}})
 
     async def close(self):
         for r in self._http_runners.values():

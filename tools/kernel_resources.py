@@ -34,6 +34,7 @@ HOT = [
     "aios::gemm_ring_kernel<*",
     "aios::sample_kernel*",
     "aios::logprob_kernel*",
+    "aios::embed_pool_kernel<*",
     "aios::get_rows_step_kernel*",
 ]
 
