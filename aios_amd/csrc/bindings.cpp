@@ -248,6 +248,31 @@ PYBIND11_MODULE(_engine, m) {
            py::arg("slot"), py::arg("tokens"), py::arg("start_pos") = 0, py::arg("pooling") = (int)EMBED_MEAN,
            py::arg("final") = true)
       .def("embed_tokens", &Engine::embed_tokens)
+      .def("score_prefill",
+           [](Engine& e, int slot, const std::vector<int>& tokens, int start_pos, int next_token, int top_n,
+              bool want_logits) {
+             // dict of numpy arrays: lp, best_lp (float32 [T]), rank, best (int32 [T]) and, when top_n > 0,
+             // ids (int32 [T][top_n]) and lps (float32 [T][top_n])
+             Engine::PromptScores r;
+             {
+               py::gil_scoped_release nogil;
+               r = e.score_prefill(slot, tokens, start_pos, next_token, top_n, want_logits);
+             }
+             const py::ssize_t T = (py::ssize_t)r.lp.size();
+             py::dict d;
+             d["lp"] = py::array_t<float>(T, r.lp.data());
+             d["best_lp"] = py::array_t<float>(T, r.best_lp.data());
+             d["rank"] = py::array_t<int>(T, r.rank.data());
+             d["best"] = py::array_t<int>(T, r.best.data());
+             if (top_n > 0) {
+               d["ids"] = py::array_t<int>({T, (py::ssize_t)top_n}, r.ids.data());
+               d["lps"] = py::array_t<float>({T, (py::ssize_t)top_n}, r.lps.data());
+             }
+             return d;
+           },
+           py::arg("slot"), py::arg("tokens"), py::arg("start_pos") = 0, py::arg("next_token") = -1,
+           py::arg("top_n") = 0, py::arg("want_logits") = false)
+      .def("score_group_rows", &Engine::score_group_rows)
       .def("decode",
            [](Engine& e, const std::vector<int>& slots, const std::vector<int>& tokens, const std::vector<int>& pos,
               const std::vector<float>& temperature, const std::vector<int>& top_k, uint64_t seed, py::bytes mask,
@@ -775,6 +800,18 @@ PYBIND11_MODULE(_engine, m) {
         },
         py::arg("logits"), py::arg("ldl"), py::arg("B"), py::arg("V"), py::arg("tokens"), py::arg("top_n"),
         py::arg("out_lp"), py::arg("out_id"), py::arg("st"));
+  m.def("score_rows",
+        [](uintptr_t logits, int ldl, int R, int V, uintptr_t targets, uintptr_t out_f, uintptr_t out_i, uintptr_t st,
+           int max_grid) {
+          // out_f / out_i: [R][2]; max_grid: workgroups at most (0: the launcher's cap), for the grid stride
+          ScoreArgs a;
+          std::memset(&a, 0, sizeof(a));
+          a.logits = (const float*)logits; a.ldl = ldl; a.R = R; a.V = V;
+          a.targets = (const int*)targets; a.out_f = (float*)out_f; a.out_i = (int*)out_i; a.max_grid = max_grid;
+          launch_score_rows(a, S(st));
+        },
+        py::arg("logits"), py::arg("ldl"), py::arg("R"), py::arg("V"), py::arg("targets"), py::arg("out_f"),
+        py::arg("out_i"), py::arg("st"), py::arg("max_grid") = 0);
   m.attr("EMBED_NONE") = (int)EMBED_NONE;
   m.attr("EMBED_MEAN") = (int)EMBED_MEAN;
   m.attr("EMBED_LAST") = (int)EMBED_LAST;

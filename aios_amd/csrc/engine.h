@@ -128,6 +128,29 @@ class Engine {
   // (start_pos + T) x d normed rows, staged on the device and copied out once.  Single-GPU engines only.
   std::vector<float> embed_prefill(int slot, const std::vector<int>& tokens, int start_pos, int pooling, bool final);
   int embed_tokens() const { return emb_tokens_; }  // tokens pooled by the last final embed_prefill
+  // Prompt scoring (ops.h ScoreArgs: the rule).  Runs exactly the forward and KV writes of
+  // prefill(slot, tokens, start_pos, want_logits) and after each internal chunk scores that chunk's hidden
+  // rows in groups: output_norm + lm_head of the group into a scoring logits buffer [group rows][V], the
+  // row-scoring kernel, and, when top_n > 0, the logprob kernel over the same rows for the alternatives.
+  // Row i's target is tokens[i + 1]; the call's last row takes next_token (-1: none -- lp NaN, rank -1; a
+  // chunked caller passes the next chunk's first token).  The scoring buffer is allocated by the first call
+  // and bounded independently of the chunk: SCORE_LOGITS_BYTES of logits, i.e. that many bytes / (4 V) rows
+  // per group (at least SCORE_MIN_ROWS, at most the prefill chunk).  The call's results are staged on the
+  // device and copied out once.  want_logits: the last row's logits are also left in logits_ row 0 by the
+  // lm_head(1, ...) call prefill makes, so sample_first and the decode steps behave as after prefill (the
+  // host copy of that row is not returned).  top_n in 0..LOGPROB_MAX_TOP; a vocabulary above SAMPLE_MAX_V is
+  // refused only when top_n > 0.  Single-GPU engines only: a vocab-parallel lm_head shards the row.
+  static constexpr size_t SCORE_LOGITS_BYTES = (size_t)64 << 20;
+  static constexpr int SCORE_MIN_ROWS = 64;
+  struct PromptScores {
+    std::vector<float> lp, best_lp;  // [T]
+    std::vector<int> rank, best;     // [T]
+    std::vector<int> ids;            // [T][top_n], only when top_n > 0
+    std::vector<float> lps;          // [T][top_n], only when top_n > 0
+  };
+  PromptScores score_prefill(int slot, const std::vector<int>& tokens, int start_pos, int next_token, int top_n,
+                             bool want_logits);
+  int score_group_rows() const;  // rows per lm_head group for this model
   // One decode step for B sequences: input token ids at positions pos[b] in slots[b].  Samples
   // with per-row temperature/top_k (0 = greedy) and optional grammar bitmasks; returns tokens.
   std::vector<int> decode(const std::vector<int>& slots, const std::vector<int>& tokens, const std::vector<int>& pos,
@@ -311,11 +334,30 @@ class Engine {
     int slot, pooling;
     bool final;
   };
-  // prefill()'s body; fold: each chunk's rows also go through embed_fold
+  // score_prefill's hook, in the same place: each chunk's hidden rows go through score_fold (null: nothing
+  // is enqueued for it)
+  struct ScoreFold {
+    int top_n;
+    int T;  // rows of the call (the staged results' layout)
+  };
+  // prefill()'s body; fold: each chunk's rows also go through embed_fold; score: ... through score_fold
   std::vector<float> prefill_run(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
-                                 const EmbedFold* fold);
+                                 const EmbedFold* fold, const ScoreFold* score = nullptr);
   void prefill_gemm(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
-                    const EmbedFold* fold = nullptr);
+                    const EmbedFold* fold = nullptr, const ScoreFold* score = nullptr);
+  // n hidden rows x[n][d], rows [row0, row0 + n) of the call being scored
+  void score_fold(const ScoreFold& f, const float* x, int n, int row0);
+  void score_lm_head(int n, const float* x, int ldx);  // sc_logits_[n][V] = rmsnorm(x) . output^T
+  void score_buffers();                    // allocated by the first score_prefill
+  int sc_rows_ = 0;                        // rows of the scoring logits buffer = rows per lm_head group
+  float* sc_logits_ = nullptr;             // [sc_rows_][V]
+  int* sc_targets_ = nullptr;              // [max_ctx] the call's targets
+  char* sc_out_ = nullptr;                 // the call's staged results: [T][2] f | [T][2] i | [T][LOGPROB_ROW] f | ... i
+  int* sc_topn_ = nullptr;                 // [sc_rows_] the logprob launch's per-row top_n
+  void* sc_lp_ws_ = nullptr;               // its workspace and tickets for sc_rows_ rows (vocabularies it takes)
+  size_t sc_lp_ws_bytes_ = 0;
+  int* sc_lp_cnt_ = nullptr;
+  int sc_topn_val_ = -1;                   // the value sc_topn_ holds
   // n hidden rows x[n][d] of positions [pos0, pos0 + n) of f.slot; last: the call's last chunk
   void embed_fold(const EmbedFold& f, const float* x, int n, int pos0, bool last);
   void embed_buffers(bool rows);           // allocated by the first embed_prefill (rows: by the first EMBED_NONE)

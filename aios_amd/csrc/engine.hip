@@ -1316,7 +1316,7 @@ bool Engine::gemm_prefill_ok(int T) const { return gm_ok_ && T >= gm_min_rows_; 
 // so every weight byte is dequantised once per chunk (not once per 8 rows as on the GEMV path).
 // TP: the row-parallel O / down outputs go through the all-reduce hook into the residual.
 void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
-                          const EmbedFold* fold) {
+                          const EmbedFold* fold, const ScoreFold* score) {
   TraceRange tr("aios.prefill_gemm");
   const int T = (int)tokens.size();
   const int d = cfg_.d_model, hd = cfg_.head_dim, H = cfg_.n_heads, Hkv = cfg_.n_kv_heads, ff = cfg_.d_ff;
@@ -1430,6 +1430,7 @@ void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_po
     }
     if (r0 + n == T && want_logits) lm_head(1, gm_x_ + (size_t)(n - 1) * d, d);
     if (fold) embed_fold(*fold, gm_x_, n, start_pos + r0, r0 + n == T);
+    if (score) score_fold(*score, gm_x_, n, r0);
   }
 }
 
@@ -1438,7 +1439,7 @@ std::vector<float> Engine::prefill(int slot, const std::vector<int>& tokens, int
 }
 
 std::vector<float> Engine::prefill_run(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
-                                       const EmbedFold* fold) {
+                                       const EmbedFold* fold, const ScoreFold* score) {
   const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
   TraceRange tr("aios.prefill");
   if (!finalized_) throw std::runtime_error("engine not finalized");
@@ -1452,7 +1453,7 @@ std::vector<float> Engine::prefill_run(int slot, const std::vector<int>& tokens,
   kv_prepare_write(slot, start_pos, start_pos + T);
   kv_sync(0);
   if (gemm_prefill_ok(T)) {
-    prefill_gemm(slot, tokens, start_pos, want_logits, fold);
+    prefill_gemm(slot, tokens, start_pos, want_logits, fold, score);
     std::vector<float> out;
     if (want_logits) {
       out.resize(cfg_.vocab_size);
@@ -1590,6 +1591,7 @@ std::vector<float> Engine::prefill_run(int slot, const std::vector<int>& tokens,
       x_ = xb; q_ = qb; qkv_ = qkvb; attn_ = ab; ff_ = fb;
       if (r0 + n == T && want_logits) lm_head(1, x_ + (size_t)(n - 1) * d, d);
       if (fold) embed_fold(*fold, x_, n, start_pos + r0, r0 + n == T);
+      if (score) score_fold(*score, x_, n, r0);
     }
   } catch (...) {
     std::swap(x_, pf_x_); std::swap(q_, pf_q_); std::swap(qkv_, pf_qkv_); std::swap(attn_, pf_attn_);
@@ -1682,6 +1684,142 @@ std::vector<float> Engine::embed_prefill(int slot, const std::vector<int>& token
                            hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
   return out;
+}
+
+// ---- prompt scoring (engine.h score_prefill) --------------------------------------------------------
+int Engine::score_group_rows() const {
+  const size_t rows = SCORE_LOGITS_BYTES / ((size_t)cfg_.vocab_size * 4);
+  // (at most the prefill chunk: gm_a16_ holds the group's normed rows; the GEMV path's chunks are shorter)
+  return (int)std::min<size_t>(std::max<size_t>(rows, SCORE_MIN_ROWS), (size_t)std::max(gm_ok_ ? gm_rows_ : prefill_rows_, 1));
+}
+
+void Engine::score_buffers() {
+  // First use, not finalize, and all or nothing, as embed_buffers
+  if (sc_logits_) return;
+  const int V = cfg_.vocab_size, rows = score_group_rows();
+  const size_t ctx = (size_t)cfg_.max_ctx;
+  float* lg = (float*)dmalloc((size_t)rows * V * 4);
+  int* tg = (int*)dmalloc(ctx * 4);
+  const size_t ob = ctx * (16 + (size_t)LOGPROB_ROW * 8);
+  char* out = (char*)dmalloc(ob);
+  int* tn = (int*)dmalloc((size_t)rows * 4);
+  size_t lpb = 0;
+  void* lpw = nullptr;
+  int* lpc = nullptr;
+  if (V <= SAMPLE_MAX_V) {
+    lpb = logprob_ws_bytes(rows, V);
+    lpw = dmalloc(lpb);
+    lpc = (int*)dmalloc((size_t)rows * 4);
+    HIP_CHECK(hipMemset(lpc, 0, (size_t)rows * 4));
+    HIP_CHECK(hipStreamSynchronize(nullptr));  // (the memset ran on the null stream, the kernel runs on ours)
+  }
+  sc_rows_ = rows; sc_targets_ = tg; sc_out_ = out; sc_topn_ = tn; sc_topn_val_ = -1;
+  sc_lp_ws_ = lpw; sc_lp_ws_bytes_ = lpb; sc_lp_cnt_ = lpc;
+  sc_logits_ = lg;
+  ws_bytes_ += (size_t)rows * V * 4 + ctx * 4 + ob + (size_t)rows * 4 + lpb + (lpc ? (size_t)rows * 4 : 0);
+}
+
+// sc_logits_[n][V] = rmsnorm(x) . output^T for n <= sc_rows_ rows: lm_head with an output pointer and a row
+// count.  Five rows or more go through the GEMMs (the ring GEMM up to 32, the prefill GEMM above) where the
+// prefill does, shorter groups and engines without the GEMM path through the GEMV in sub-batches of 8.
+void Engine::score_lm_head(int n, const float* x, int ldx) {
+  const int d = cfg_.d_model, V = cfg_.vocab_size;
+  if (gm_ok_ && n >= 5 && n <= gm_rows_ && V % 64 == 0 && gemm_supports(output_.w.qtype)) {
+    launch_rmsnorm_bf16(x, ldx, out_norm_, gm_a16_, d, n, d, cfg_.norm_eps, stream_);
+    GemmQArgs g;
+    std::memset(&g, 0, sizeof(g));
+    g.A = gm_a16_; g.lda = d; g.M = n; g.K = d; g.nseg = 1; g.seg[0] = output_.w; g.N = V;
+    g.C = sc_logits_; g.ldc = V; g.epi = GEPI_STORE;
+    gemm(g);
+    return;
+  }
+  for (int o = 0; o < n; o += 8)
+    gemv({&output_}, V, d, std::min(8, n - o), x + (size_t)o * ldx, ldx, out_norm_, sc_logits_ + (size_t)o * V, V,
+         EPI_STORE, 0);
+}
+
+void Engine::score_fold(const ScoreFold& f, const float* x, int n, int row0) {
+  const int d = cfg_.d_model, V = cfg_.vocab_size;
+  const size_t T = (size_t)f.T;
+  float* out_f = (float*)sc_out_;
+  int* out_i = (int*)(sc_out_ + T * 8);
+  float* alt_lp = (float*)(sc_out_ + T * 16);
+  int* alt_id = (int*)(sc_out_ + T * 16 + T * LOGPROB_ROW * 4);
+  for (int g0 = 0; g0 < n; g0 += sc_rows_) {
+    const int m = std::min(sc_rows_, n - g0);
+    const size_t r = (size_t)row0 + g0;
+    score_lm_head(m, x + (size_t)g0 * d, d);
+    ScoreArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.logits = sc_logits_; a.ldl = V; a.R = m; a.V = V;
+    a.targets = sc_targets_ + r; a.out_f = out_f + r * 2; a.out_i = out_i + r * 2;
+    launch_score_rows(a, stream_);
+    if (f.top_n > 0) {
+      LogprobArgs p;
+      std::memset(&p, 0, sizeof(p));
+      p.logits = sc_logits_; p.ldl = V; p.B = m; p.V = V;
+      p.tokens = sc_targets_ + r;  // (the kernel clamps a -1; only the alternatives are read back)
+      p.top_n = sc_topn_;
+      p.out_lp = alt_lp + r * LOGPROB_ROW; p.out_id = alt_id + r * LOGPROB_ROW;
+      p.ws = sc_lp_ws_; p.ws_bytes = sc_lp_ws_bytes_; p.counters = sc_lp_cnt_;
+      launch_logprobs(p, stream_);
+    }
+  }
+}
+
+Engine::PromptScores Engine::score_prefill(int slot, const std::vector<int>& tokens, int start_pos, int next_token,
+                                           int top_n, bool want_logits) {
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  if (cfg_.tp_size > 1) throw std::runtime_error("score_prefill: single-GPU engines only");
+  if (top_n < 0 || top_n > LOGPROB_MAX_TOP)
+    throw std::runtime_error("score_prefill: top_n outside 0.." + std::to_string(LOGPROB_MAX_TOP));
+  const int V = cfg_.vocab_size, T = (int)tokens.size();
+  if (top_n > 0 && V > SAMPLE_MAX_V)
+    throw std::runtime_error("score_prefill: alternatives need a vocabulary up to " + std::to_string(SAMPLE_MAX_V));
+  if (next_token < -1 || next_token >= V) throw std::runtime_error("score_prefill: next_token out of range");
+  if (T == 0) throw std::runtime_error("score_prefill: empty prompt");
+  if (start_pos < 0 || start_pos + T > cfg_.max_ctx) throw std::runtime_error("score_prefill: context overflow");
+  for (int t : tokens)
+    if (t < 0 || t >= V) throw std::runtime_error("score_prefill: token id out of range");
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  score_buffers();
+  std::vector<int> tg(T);
+  for (int i = 0; i + 1 < T; ++i) tg[i] = tokens[i + 1];
+  tg[T - 1] = next_token;
+  HIP_CHECK(hipMemcpyAsync(sc_targets_, tg.data(), (size_t)T * 4, hipMemcpyHostToDevice, stream_));
+  if (top_n > 0 && sc_topn_val_ != top_n) {
+    const std::vector<int> tn(sc_rows_, top_n);
+    HIP_CHECK(hipMemcpyAsync(sc_topn_, tn.data(), tn.size() * 4, hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));  // (tn leaves scope)
+    sc_topn_val_ = top_n;
+  }
+  const ScoreFold sf{top_n, T};
+  prefill_run(slot, tokens, start_pos, want_logits, nullptr, &sf);
+  // one copy of what the call staged: [T][2] floats | [T][2] ints (| [T][LOGPROB_ROW] floats | ... ints)
+  const size_t nbytes = (size_t)T * (16 + (top_n > 0 ? (size_t)LOGPROB_ROW * 8 : 0));
+  std::vector<char> host(nbytes);
+  HIP_CHECK(hipMemcpyAsync(host.data(), sc_out_, nbytes, hipMemcpyDeviceToHost, stream_));
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  const float* hf = (const float*)host.data();
+  const int* hi = (const int*)(host.data() + (size_t)T * 8);
+  PromptScores r;
+  r.lp.resize(T); r.best_lp.resize(T); r.rank.resize(T); r.best.resize(T);
+  for (int i = 0; i < T; ++i) {
+    r.lp[i] = hf[2 * i]; r.best_lp[i] = hf[2 * i + 1];
+    r.rank[i] = hi[2 * i]; r.best[i] = hi[2 * i + 1];
+  }
+  if (top_n > 0) {
+    const float* al = (const float*)(host.data() + (size_t)T * 16);
+    const int* ai = (const int*)(host.data() + (size_t)T * 16 + (size_t)T * LOGPROB_ROW * 4);
+    r.ids.resize((size_t)T * top_n);
+    r.lps.resize((size_t)T * top_n);
+    for (int i = 0; i < T; ++i)
+      for (int j = 0; j < top_n; ++j) {
+        r.ids[(size_t)i * top_n + j] = ai[(size_t)i * LOGPROB_ROW + 1 + j];
+        r.lps[(size_t)i * top_n + j] = al[(size_t)i * LOGPROB_ROW + 1 + j];
+      }
+  }
+  return r;
 }
 
 std::vector<int> Engine::decode(const std::vector<int>& slots, const std::vector<int>& tokens,

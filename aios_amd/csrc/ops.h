@@ -236,6 +236,26 @@ struct LogprobArgs {
 void launch_logprobs(const LogprobArgs& a, hipStream_t st);
 size_t logprob_ws_bytes(int B, int V);
 
+// Prompt scoring: the same RAW distribution for MANY rows, one target id each (a prompt's next tokens).
+// Per row r, l = logits[r][0..V), t = targets[r], lse = log sum_i exp(l_i):
+//   out_f[r] = {lp, best_lp}, out_i[r] = {rank, best};  lp = l[t] - lse;
+//   rank = #{ i : l_i > l_t, or l_i == l_t and i < t } (0: the target is the argmax);
+//   best = the lowest id among the maxima, best_lp = l[best] - lse.
+// t < 0 (or, on the device, t >= V): no target -- lp NaN, rank -1, best / best_lp still reported.  A -inf logit
+// has logprob -inf; a row that is all -inf or holds a NaN is unspecified.  Any V >= 1 (the kernel loops: no
+// SAMPLE_MAX_V limit), any ldl >= V (nothing in [V, ldl) is read), any R.  No workspace, no atomics: the same
+// input gives the same bits.  kernels/score_rows.hip; tests/score_oracle.py is this rule in float64.
+struct ScoreArgs {
+  const float* logits;  // [R][ldl]
+  int ldl;
+  int R, V;
+  const int* targets;   // [R]
+  float* out_f;         // [R][2]
+  int* out_i;           // [R][2]
+  int max_grid = 0;     // workgroups at most (0: the launcher's cap); more rows take a grid stride
+};
+void launch_score_rows(const ScoreArgs& a, hipStream_t st);
+
 // ---- text embeddings ---------------------------------------------------------------------------
 // Pooled embedding of hidden rows x[t] (the residual stream before output_norm), llama.cpp's --embedding
 // rule for a causal model:  h[t] = x[t] * g * rsqrt(mean(x[t]^2) + eps)  (the model's final RMSNorm);

@@ -340,6 +340,11 @@ class TPEngine:
             # sharded; the shard's own Engine.set_logprobs throws): the scheduler sees no such method,
             # refuses the request alone, and the HTTP endpoint answers 400
             raise AttributeError(name)
+        if name in ("score_prefill", "score_group_rows"):
+            # no prompt scoring on a tensor-parallel tier (the shard's Engine.score_prefill throws "single-GPU
+            # engines only": a vocab-parallel lm_head shards the row): hidden like the logprob calls, so the
+            # scheduler fails that request alone and /v1/completions answers 400 for echo + logprobs
+            raise AttributeError(name)
         if name in ("embed_prefill", "embed_tokens"):
             # no embeddings on a tensor-parallel tier (the shard's Engine.embed_prefill throws "single-GPU
             # engines only"; the hidden state is replicated, so this is scope, not design): hidden like the

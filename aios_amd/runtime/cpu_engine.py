@@ -19,6 +19,7 @@ import torch
 from ..models.reference import ReferenceModel
 from . import embedding as host_embedding
 from . import sampler as host_sampler
+from . import scoring as host_scoring
 
 
 @dataclasses.dataclass
@@ -129,6 +130,23 @@ class CpuEngine:
 
     def embed_tokens(self) -> int:
         return self._emb_tokens
+
+    def score_prefill(self, slot: int, ids: List[int], start: int = 0, next_token: int = -1, top_n: int = 0,
+                      want_logits: bool = False) -> dict:
+        """The native Engine's score_prefill (runtime/scoring.py: the rule): prefill `ids` into the slot and
+        score every row against the token after it, the last row against next_token (-1: none).  The same
+        dict of arrays; want_logits: the last row's logits are kept for sample_first, as after prefill."""
+        if not ids:
+            raise ValueError("score_prefill: empty prompt")
+        if start + len(ids) > self.config.max_ctx:
+            raise ValueError("score_prefill: context overflow")
+        if not -1 <= int(next_token) < self.config.vocab_size:
+            raise ValueError("score_prefill: next_token out of range")
+        c = self._cache_at(slot, start)
+        logits = self.model.forward(list(ids), c).numpy()
+        if want_logits:
+            self.last = logits[-1][None]
+        return host_scoring.score_rows(logits, [int(t) for t in ids[1:]] + [int(next_token)], top_n)
 
     def set_sample_processors(self, min_p, repeat_penalty, presence_penalty, frequency_penalty, recent):
         """Per-row min-p, penalties and penalty windows (the rows' recent token ids) for the NEXT

@@ -78,6 +78,11 @@ class GenRequest:
     # embed_prefill and the request ends with it -- GenResult.embedding, finish_reason "embedding";
     # max_tokens, json_mode, the sampling fields and logprobs are ignored
     embed: Optional[str] = None
+    # logprobs of the PROMPT's tokens (runtime/scoring.py: the rule; the engine's score_prefill): None = off,
+    # else the number of alternatives per prompt token, 0..20 -- GenResult.prompt_logprobs.  The prompt is
+    # prefilled from position 0 (cached positions have no logits) and generation proceeds as usual; with
+    # such a request max_tokens may be 0: it then finishes "length" with no sampled token
+    prompt_logprobs: Optional[int] = None
     stop_ids: Optional[List[int]] = None
     on_delta: Optional[Callable[[str], None]] = None
     on_done: Optional[Callable[["GenResult"], None]] = None
@@ -102,11 +107,15 @@ class GenResult:
     logprobs: Optional[list] = None
     # requests with embed set: the unit vector [d] ("mean", "last") or the normed rows [tokens, d] ("none")
     embedding: Optional[np.ndarray] = None
+    # requests with prompt_logprobs set: one (token id, logprob | None, rank | None, [(alternative id,
+    # logprob), ...]) per prompt token; rank 0 = the token was the model's argmax, the alternatives are the
+    # best tokens AT that position, best first; the first token has no distribution: None, None, []
+    prompt_logprobs: Optional[list] = None
 
 
 class _Seq:
     __slots__ = ("req", "slot", "pos", "last", "out", "grammar_state", "emitted", "t_first", "cached", "todo",
-                 "p_off", "r_off", "seed", "proc", "pen_n", "lp_n", "lps", "embedding")
+                 "p_off", "r_off", "seed", "proc", "pen_n", "lp_n", "lps", "embedding", "plp_n", "plps")
 
     def __init__(self, req, slot):
         self.req, self.slot = req, slot
@@ -126,6 +135,8 @@ class _Seq:
         self.lp_n = int(req.top_logprobs) if req.logprobs else -1  # alternatives per token; -1: no logprobs
         self.lps: List[tuple] = []   # one entry per token of `out`
         self.embedding = None        # an embedding request's result
+        self.plp_n = -1              # prompt logprobs: alternatives per prompt token; -1: not asked
+        self.plps: List[tuple] = []  # one entry per prompt token prefilled so far
         self.p_off = 0               # incremental detokenization window [p_off, r_off) already emitted
         self.r_off = 0
 
@@ -147,6 +158,8 @@ class Scheduler:
         self.can_logprobs = hasattr(engine, "set_logprobs") and hasattr(engine, "last_logprobs")
         # text embeddings need the engine's embed_prefill (a tensor-parallel tier hides it)
         self.can_embed = hasattr(engine, "embed_prefill")
+        # prompt logprobs need the engine's score_prefill (a tensor-parallel tier has none)
+        self.can_score = hasattr(engine, "score_prefill")
         self.tok = tokenizer
         self.max_batch = max_batch
         self.max_ctx = max_ctx
@@ -172,7 +185,7 @@ class Scheduler:
         self.cv = threading.Condition()
         self.stop_flag = False
         self.stats = dict(requests=0, tokens=0, prefill_tokens=0, cached_tokens=0, steps=0, batch_sum=0, errors=0,
-                          embeddings=0)
+                          embeddings=0, prompt_scores=0)
         # health / metrics (ModelManager.supervise and HealthCheck details)
         self.max_slots = max_slots
         self.last_progress = time.time()   # last completed admission or decode step
@@ -339,18 +352,32 @@ class Scheduler:
         if r.embed is not None:
             return self._admit_embedding(r)
         ids = r.prompt_ids
-        if len(ids) >= self.max_ctx:
+        score = r.prompt_logprobs is not None
+        if score:
+            if isinstance(r.prompt_logprobs, bool) or not 0 <= int(r.prompt_logprobs) <= host_sampler.LOGPROB_MAX_TOP:
+                raise ValueError(f"prompt_logprobs outside 0..{host_sampler.LOGPROB_MAX_TOP}")
+            if not self.can_score:
+                raise ValueError(f"{self.name}: this tier's engine cannot score prompts")
+            if not ids:
+                raise ValueError("prompt is empty")
+        # (a pure scoring request generates nothing: the whole window may be prompt)
+        if len(ids) >= self.max_ctx and not (score and r.max_tokens <= 0 and len(ids) == self.max_ctx):
             raise ValueError(f"prompt of {len(ids)} tokens exceeds the context window ({self.max_ctx})")
         if r.logprobs:
             if not 0 <= int(r.top_logprobs) <= host_sampler.LOGPROB_MAX_TOP:
                 raise ValueError(f"top_logprobs outside 0..{host_sampler.LOGPROB_MAX_TOP}")
             if not self.can_logprobs:
                 raise ValueError(f"{self.name}: this tier's engine cannot report logprobs")
-        r.max_tokens = max(1, min(r.max_tokens, self.max_ctx - len(ids)))
+        r.max_tokens = max(0 if score else 1, min(r.max_tokens, self.max_ctx - len(ids)))
         r.min_tokens = min(r.min_tokens, r.max_tokens)
-        slot, common = self._pick_slot(ids)
+        if score:  # cached positions have no logits to score: from position 0, in the least useful slot
+            slot, common = min(self.free_slots, key=lambda f: len(self.slot_cache[f])), 0
+        else:
+            slot, common = self._pick_slot(ids)
         self.free_slots.remove(slot)
         seq = _Seq(r, slot)
+        if score:
+            seq.plp_n = int(r.prompt_logprobs)
         d = self.sampling_defaults
         proc = tuple(float(d[k] if getattr(r, k) is None else getattr(r, k)) for k in NEUTRAL_PROCESSORS)
         if proc != tuple(NEUTRAL_PROCESSORS.values()):
@@ -370,6 +397,11 @@ class Scheduler:
         tp0 = time.perf_counter()
         if r.embed is not None:
             emb = self.engine.embed_prefill(seq.slot, chunk, seq.pos, host_embedding.POOLING[r.embed], last)
+        elif seq.plp_n >= 0:
+            # the last row's target is the next chunk's first token; the prompt's last row has none
+            sc = self.engine.score_prefill(seq.slot, chunk, seq.pos, -1 if last else int(seq.todo[n]), seq.plp_n,
+                                           last and r.max_tokens > 0)
+            self._take_scores(seq, chunk, sc, last)
         else:
             logits = self.engine.prefill(seq.slot, chunk, seq.pos, last)
         self.timing["prefill_s"] += time.perf_counter() - tp0
@@ -385,6 +417,13 @@ class Scheduler:
             self.stats["embeddings"] += 1
             self._finish(seq, "embedding")
             return
+        if seq.plp_n >= 0:
+            self.stats["prompt_scores"] += 1
+            if r.max_tokens <= 0:  # a pure scoring request: no token is sampled
+                self._finish(seq, "length")
+                return
+            if not hasattr(self.engine, "sample_first"):
+                logits = np.asarray(self.engine.last_logits(1), np.float32)
         self.prefilling.remove(seq)
         mask = None
         if r.json_mode and self.grammar is not None:
@@ -414,6 +453,18 @@ class Scheduler:
         seq.t_first = time.time()
         self.active.append(seq)
         self._accept(seq, tok, lp)
+
+    @staticmethod
+    def _take_scores(seq: _Seq, chunk: List[int], sc: dict, last: bool):
+        """Append a score_prefill result to seq.plps: row i of the chunk scored the token after it."""
+        if seq.pos == 0:
+            seq.plps.append((int(chunk[0]), None, None, []))
+        targets = list(chunk[1:]) + ([] if last else [int(seq.todo[len(chunk)])])
+        lp, rank = sc["lp"], sc["rank"]
+        ids, lps = (sc["ids"], sc["lps"]) if seq.plp_n > 0 else (None, None)
+        for i, t in enumerate(targets):
+            top = [(int(a), float(x)) for a, x in zip(ids[i], lps[i]) if a >= 0] if ids is not None else []
+            seq.plps.append((int(t), float(lp[i]), int(rank[i]), top))
 
     def _accept(self, seq: _Seq, tok: int, lp=None) -> bool:
         """Record a sampled token (lp: its logprob entry, kept only with a token that is emitted);
@@ -686,7 +737,8 @@ class Scheduler:
             text=text, token_ids=list(seq.out), prompt_tokens=len(r.prompt_ids), completion_tokens=len(seq.out),
             finish_reason=reason, ttft_ms=(seq.t_first - r.submitted_at) * 1e3 if seq.t_first else 0.0,
             latency_ms=(now - r.submitted_at) * 1e3, cached_prompt_tokens=seq.cached, error=error,
-            logprobs=list(seq.lps) if seq.lp_n >= 0 else None, embedding=seq.embedding))
+            logprobs=list(seq.lps) if seq.lp_n >= 0 else None, embedding=seq.embedding,
+            prompt_logprobs=list(seq.plps) if seq.plp_n >= 0 else None))
 
     @staticmethod
     def _done(r: GenRequest, res: GenResult):

@@ -7,7 +7,8 @@ decoding, App. A #3), tokens_used = prompt + completion, latency_ms = wall time.
 streams real token deltas as they are generated (App. A #2).
 
 HTTP (per loaded model on its `ModelStatus.port`, like llama-server): POST /v1/chat/completions
-(+ `stream: true` SSE, `response_format: {"type":"json_object"}`) and GET /health -- so the
+(+ `stream: true` SSE, `response_format: {"type":"json_object"}`), POST /v1/completions, POST
+/v1/embeddings and GET /health -- so the
 gateway's `local` provider (`LOCAL_LLM_URL`, default :8082) can reach the local strategic tier.
 """
 from __future__ import annotations
@@ -135,6 +136,132 @@ def embedding_inputs(body: dict, tokenizer, max_ctx: int) -> List[List[int]]:
             raise ValueError(f"input {i}: {len(ids)} tokens exceed the context window ({max_ctx})")
         out.append(ids)
     return out
+
+
+COMPLETION_MAX_TOKENS = 16  # OpenAI's default for /v1/completions
+
+
+def completion_request(body: dict, tokenizer, scheduler) -> dict:
+    """A /v1/completions body, checked: dict(ids, prompt_text, max_tokens, temperature, echo, logprobs (None or
+    the number of alternatives), stream, sampling, repeat_last_n).  A string prompt gets BOS and no chat
+    template.  ValueError (-> 400) for what this endpoint does not serve."""
+    def is_int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+
+    if not isinstance(body, dict):
+        raise ValueError("the body must be a JSON object")
+    for k, why in (("best_of", "best_of is not supported"), ("suffix", "suffix is not supported")):
+        if body.get(k) is not None:
+            raise ValueError(why)
+    if body.get("n") not in (None, 1):
+        raise ValueError("n > 1 is not supported")
+    prompt = body.get("prompt")
+    if isinstance(prompt, str):
+        if not prompt:
+            raise ValueError("prompt is empty")
+        ids = tokenizer.encode(prompt, add_bos=True, parse_special=False)
+        text = prompt
+    elif isinstance(prompt, list) and prompt and all(is_int(t) for t in prompt):
+        ids = [int(t) for t in prompt]
+        if any(not 0 <= t < tokenizer.vocab_size for t in ids):
+            raise ValueError(f"prompt: token id outside [0, {tokenizer.vocab_size})")
+        text = tokenizer.decode(ids)
+    elif isinstance(prompt, list) and prompt:
+        raise ValueError("one prompt per request: a string or a list of token ids (lists of prompts are not supported)")
+    else:
+        raise ValueError("prompt must be a non-empty string or a non-empty list of token ids")
+    max_tokens = body.get("max_tokens")
+    max_tokens = COMPLETION_MAX_TOKENS if max_tokens is None else max_tokens
+    if not is_int(max_tokens) or max_tokens < 0:
+        raise ValueError("max_tokens must be a non-negative integer")
+    echo = body.get("echo")
+    if echo is not None and not isinstance(echo, bool):
+        raise ValueError("echo must be a boolean")
+    lp = body.get("logprobs")
+    if lp is not None and (not is_int(lp) or not 0 <= lp <= LOGPROB_MAX_TOP):
+        raise ValueError(f"logprobs must be null or an integer in 0..{LOGPROB_MAX_TOP}")
+    stream = bool(body.get("stream"))
+    if stream and lp is not None:
+        raise ValueError("logprobs are not available with stream: true")
+    if max_tokens == 0 and not (echo and lp is not None):
+        raise ValueError("max_tokens: 0 scores the prompt: it needs echo: true and logprobs")
+    if len(ids) > scheduler.max_ctx or (max_tokens > 0 and len(ids) >= scheduler.max_ctx):
+        raise ValueError(f"prompt of {len(ids)} tokens exceeds the context window ({scheduler.max_ctx})")
+    if lp is not None:  # (a tensor-parallel tier: vocab-parallel lm_head)
+        if max_tokens > 0 and not getattr(scheduler, "can_logprobs", False):
+            raise ValueError("this model's engine cannot report logprobs")
+        if echo and not getattr(scheduler, "can_score", False):
+            raise ValueError("this model's engine cannot score prompts (single-GPU tiers only)")
+    try:
+        sampling = sampling_from_body(body)
+        temperature = float(body.get("temperature", 1.0) if body.get("temperature") is not None else 1.0)
+        rln = body.get("repeat_last_n")
+        rln = None if rln is None else int(rln)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"bad sampling field: {e}") from None
+    return dict(ids=ids, prompt_text=text, max_tokens=int(max_tokens), temperature=max(temperature, 0.0),
+                echo=bool(echo), logprobs=lp, stream=stream, sampling=sampling, repeat_last_n=rln)
+
+
+def completion_logprobs(tokenizer, entries) -> dict:
+    """OpenAI's text_completion `logprobs` object from (token id, logprob | None, [(alternative id, logprob),
+    ...]) entries: tokens, token_logprobs, top_logprobs (one {token text: logprob} dict per token; colliding
+    token texts keep the better one) and text_offset (each token's offset in the tokens' concatenation).  An
+    entry whose logprob is None (a prompt's first token) reports null for both."""
+    def num(lp):
+        finite = lp == lp and lp not in (float("inf"), float("-inf"))
+        return float(lp) if finite else LOGPROB_NEG_INF
+
+    def piece(tid):
+        return tokenizer.token_bytes(int(tid)).decode("utf-8", errors="replace")
+
+    out = {"tokens": [], "token_logprobs": [], "top_logprobs": [], "text_offset": []}
+    off = 0
+    for tid, lp, top in entries:
+        s = piece(tid)
+        out["tokens"].append(s)
+        out["text_offset"].append(off)
+        off += len(s)
+        if lp is None:
+            out["token_logprobs"].append(None)
+            out["top_logprobs"].append(None)
+            continue
+        out["token_logprobs"].append(num(lp))
+        alts: Dict[str, float] = {}
+        for i, x in top:
+            k, v = piece(i), num(x)
+            if k not in alts or v > alts[k]:
+                alts[k] = v
+        out["top_logprobs"].append(alts)
+    return out
+
+
+async def complete(m, c: dict, on_delta=None, timeout: float = 120.0) -> GenResult:
+    """Submit a checked /v1/completions request (completion_request) to the model's scheduler."""
+    loop = asyncio.get_running_loop()
+    fut = loop.create_future()
+    delta_cb = None
+    if on_delta is not None:
+        def delta_cb(d):
+            loop.call_soon_threadsafe(on_delta, d)
+    req = GenRequest(prompt_ids=c["ids"], max_tokens=c["max_tokens"], temperature=c["temperature"], on_delta=delta_cb,
+                     on_done=lambda res: loop.call_soon_threadsafe(lambda: fut.done() or fut.set_result(res)),
+                     deadline=time.time() + timeout)
+    for k, v in c["sampling"].items():
+        setattr(req, k, v)
+    if c["repeat_last_n"] is not None:
+        req.repeat_last_n = c["repeat_last_n"]
+    if c["logprobs"] is not None:
+        if c["max_tokens"] > 0:
+            req.logprobs, req.top_logprobs = True, int(c["logprobs"])
+        if c["echo"]:
+            req.prompt_logprobs = int(c["logprobs"])
+    m.scheduler.submit(req)
+    try:
+        return await asyncio.wait_for(fut, timeout + 5)
+    except asyncio.TimeoutError:
+        req.cancelled = True
+        raise
 
 
 async def embed(m, inputs: List[List[int]], pooling: str, timeout: float = 120.0) -> List[GenResult]:
@@ -319,6 +446,7 @@ class AIRuntimeService:
         app.router.add_post("/v1/chat/completions", self._http_chat)
         app.router.add_get("/v1/models", self._http_models)
         app.router.add_post("/v1/embeddings", self._http_embeddings)
+        app.router.add_post("/v1/completions", self._http_completions)
         runner = web.AppRunner(app, access_log=None)
         await runner.setup()
         try:
@@ -393,6 +521,67 @@ class AIRuntimeService:
                       "total_tokens": res.prompt_tokens + res.completion_tokens},
             "timings": {"ttft_ms": res.ttft_ms, "latency_ms": res.latency_ms,
                         "cached_prompt_tokens": res.cached_prompt_tokens},
+        })
+
+    async def _http_completions(self, request):
+        """OpenAI's /v1/completions: a raw prompt (a string, which gets BOS and no chat template, or one token
+        list), optionally `echo` and `logprobs` (an integer: alternatives per token, 0..20) -- with both the
+        prompt's tokens are scored too (runtime/scoring.py: the rule), and max_tokens: 0 only scores."""
+        from aiohttp import web
+
+        m = request.app["model"]
+
+        def bad(msg):
+            return web.json_response({"error": {"message": msg, "type": "invalid_request_error"}}, status=400)
+
+        try:
+            body = await request.json()
+        except ValueError:
+            return bad("the body is not JSON")
+        try:
+            c = completion_request(body, m.tokenizer, m.scheduler)
+        except ValueError as e:
+            return bad(str(e))
+        created = int(time.time())
+        rid = f"cmpl-{created}{id(request) & 0xffff:04x}"
+
+        def chunk(text, finish):
+            return {"id": rid, "object": "text_completion", "created": created, "model": m.name,
+                    "choices": [{"text": text, "index": 0, "logprobs": None, "finish_reason": finish}]}
+
+        if c["stream"]:
+            resp = web.StreamResponse(headers={"Content-Type": "text/event-stream"})
+            await resp.prepare(request)
+            q: asyncio.Queue = asyncio.Queue()
+            task = asyncio.ensure_future(complete(m, c, on_delta=q.put_nowait))
+            task.add_done_callback(lambda _t: q.put_nowait(None))
+            if c["echo"]:
+                await resp.write(f"data: {json.dumps(chunk(c['prompt_text'], None))}\n\n".encode())
+            while True:
+                d = await q.get()
+                if d is None:
+                    break
+                await resp.write(f"data: {json.dumps(chunk(d, None))}\n\n".encode())
+            res = task.result()
+            end = chunk("", "length" if res.finish_reason == "length" else "stop")
+            await resp.write(f"data: {json.dumps(end)}\n\ndata: [DONE]\n\n".encode())
+            await resp.write_eof()
+            return resp
+        res = await complete(m, c)
+        if res.finish_reason == "error":
+            return web.json_response({"error": {"message": res.error or "inference failed", "type": "server_error"}},
+                                     status=500)
+        lp = None
+        if c["logprobs"] is not None:
+            entries = [(t, x, top) for t, x, _rank, top in (res.prompt_logprobs or [])] if c["echo"] else []
+            entries += list(res.logprobs or [])
+            lp = completion_logprobs(m.tokenizer, entries)
+        choice = {"text": (c["prompt_text"] if c["echo"] else "") + res.text, "index": 0, "logprobs": lp,
+                  "finish_reason": "length" if res.finish_reason == "length" else "stop"}
+        return web.json_response({
+            "id": rid, "object": "text_completion", "created": created, "model": m.name, "choices": [choice],
+            "usage": {"prompt_tokens": res.prompt_tokens, "completion_tokens": res.completion_tokens,
+                      "total_tokens": res.prompt_tokens + res.completion_tokens},
         })
 
     async def _http_embeddings(self, request):
