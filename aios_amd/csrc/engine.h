@@ -9,6 +9,7 @@
 // replayed (SURVEY.md §2.7 fusion targets, §7.6 hard part 2).  Sampled tokens are fed back on
 // device, so N decode steps need no host round trip.
 #pragma once
+#include <functional>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -272,6 +273,9 @@ class Engine {
   void enqueue_decode_step(int B);       // uses device arrays d_tokens_/d_pos_/d_seqlen_/d_slot_
   void enqueue_decode_forward(int B);    // ... up to the logits (no sampler)
   void enqueue_sample(int B, bool processors = false);  // the step's sampler (sample_mask_: with d_mask_)
+  // what every sampler launch shares: logits_, the parameter block's row arrays, workspace and tickets
+  // (mask: d_mask_ or null); the caller adds its seed source, pos and advance
+  SampleArgs sample_args(int B, bool masked) const;
   // the staged logit processors of a B-row sampler launch: uploads them, points s at them and
   // un-stages them (no-op when nothing is staged; throws when they were staged for another B)
   void take_processors(SampleArgs& s, int B);
@@ -293,6 +297,16 @@ class Engine {
     }
     ~LogprobStage() { rows = 0; }
   };
+  // Its twin for the staged logit processors: the same refusal.  No destructor: take_processors drops the
+  // staging at the sampler launch, and a call that throws before that launch keeps it, as it always did.
+  struct ProcessorStage {
+    ProcessorStage(int& staged, int B, const char* who) {
+      if (staged && staged != B) {
+        staged = 0;
+        throw std::runtime_error(std::string(who) + ": sample processors staged for another batch size");
+      }
+    }
+  };
   std::vector<int> lp_last_;             // top_n of the rows the last sampler launch reported (empty: none)
   char* h_lp_ = nullptr;                 // pinned: [max_batch] top_n | the device output block's mirror
   char* d_lp_out_ = nullptr;             // [max_batch][LOGPROB_ROW] floats | [max_batch][LOGPROB_ROW] ids
@@ -301,6 +315,7 @@ class Engine {
   size_t lp_ws_bytes_ = 0;
   int* lp_cnt_ = nullptr;
   hipGraphExec_t forward_graph(int B);
+  hipGraphExec_t graph_for(int key, const std::function<void()>& enqueue);  // captured once per key
   int cus_ = 0;                          // CUs of the stream's mask (0: the whole device)
   int kv_es_ = 2;                        // bytes per KV element (2 bf16, 1 fp8)
   std::vector<float> kv_scale_;          // [n_layers][K, V] fp8 scales (value = code * scale)
@@ -328,23 +343,30 @@ class Engine {
   uint8_t* h_mask_ = nullptr;            // pinned staging of the pipelined sampler's masks
   hipEvent_t pipe_ev_ = nullptr;         // the pipelined sampler's token copy
   bool gemm_prefill_ok(int T) const;
-  // embed_prefill's hook into the prefill: what to do with each chunk's hidden rows (null: plain prefill,
-  // nothing is enqueued for it)
+  // what embed_prefill / score_prefill do with each chunk's hidden rows (embed_fold / score_fold)
   struct EmbedFold {
     int slot, pooling;
     bool final;
   };
-  // score_prefill's hook, in the same place: each chunk's hidden rows go through score_fold (null: nothing
-  // is enqueued for it)
   struct ScoreFold {
     int top_n;
     int T;  // rows of the call (the staged results' layout)
   };
-  // prefill()'s body; fold: each chunk's rows also go through embed_fold; score: ... through score_fold
+  // A prefill call's per-chunk consumer, run on the host after each chunk's layers were enqueued.
+  struct ChunkHook {
+    // x[n][d]: the chunk's hidden rows, rows [row0, row0 + n) of the call; last: the call's last chunk
+    // (null: plain prefill, nothing is enqueued for it)
+    std::function<void(const float* x, int n, int row0, bool last)> fn;
+    // chunks that reach the prefill GEMM (more than 32 rows) ask for its plans without split-K / stream-K
+    bool deterministic = false;
+  };
+  // prefill()'s body: validate, map the KV blocks, one of the two bodies below, the logits' copy-out
   std::vector<float> prefill_run(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
-                                 const EmbedFold* fold, const ScoreFold* score = nullptr);
-  void prefill_gemm(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
-                    const EmbedFold* fold = nullptr, const ScoreFold* score = nullptr);
+                                 const ChunkHook& hook);
+  void prefill_gemm(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits, const ChunkHook& hook);
+  // short prompts / engines without the GEMM path: sub-batches of <= 8 rows through the GEMVs, on the pf_*
+  // buffers only (no decode workspace member is read or written)
+  void prefill_gemv(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits, const ChunkHook& hook);
   // n hidden rows x[n][d], rows [row0, row0 + n) of the call being scored
   void score_fold(const ScoreFold& f, const float* x, int n, int row0);
   void score_lm_head(int n, const float* x, int ldx);  // sc_logits_[n][V] = rmsnorm(x) . output^T
@@ -371,10 +393,46 @@ class Engine {
   std::vector<int> emb_pos_, emb_mode_;    // [max_slots] position reached (-1: no state) and its pooling
   int emb_tokens_ = 0;
   void layer_decode(int l, int B);
+  // ---- launch descriptors: one builder each, from (layer, rows, explicit buffers) ----
+  // one QKV group (qkv_groups) of layer l for B rows of x[B][d]: fused = RoPE + KV write in the epilogue
+  // (q out, pos / slot read), else the packed rows into qkv for qkv_post.  No knobs: the caller's.
+  GemvArgs qkv_gemv_args(int l, const std::vector<const QMat*>& grp, int row0, int B, const float* x, bool fused,
+                         float* q, float* qkv, const int* pos, const int* slot);
+  QkvPostArgs qkv_post_args(int l, const float* qkv, int ldqkv, int T, const int* pos, const int* slot, float* q_out,
+                            const float* bias, unsigned* amax) const;
+  AttnDecodeArgs attn_decode_args(int l, int B, const float* q, float* out, const int* seq_len, const int* slot,
+                                  const int* block_table, int bt_rows, float* o_part, float* ml,
+                                  bf16_t* out16 = nullptr) const;
+  // single-matrix skinny / prefill GEMM: C[M][N] (ldc) = A[M][K] . w^T with epilogue epi
+  static GemmQArgs gemm_args(const bf16_t* A, int lda, int M, int K, const QWeight& w, int N, int ldc, float* C, int epi);
+  // the stacked Q / K / V GEMM of layer l, and its RoPE + q store + KV-write epilogue (GEPI_QKV)
+  GemmQArgs qkv_gemm_args(int l, const bf16_t* A, int M, float* C) const;
+  void qkv_gemm_epi(GemmQArgs& g, int l, const int* pos, const int* slot, float* q_out) const;
+  // RMSNorm split across two GEMMs: the residual GEMM (O, down) also writes bf16(x * g_next) to xn16 and
+  // per-tile row sums of squares to part; the next GEMM reads xn16 as A and scales its rows by the inverse RMS
+  struct SplitNorm {
+    bf16_t* xn16;
+    float* part;
+    int parts;
+  };
+  void nrm_consume(GemmQArgs& g, const SplitNorm& n) const;
+  static void nrm_produce(GemmQArgs& g, const SplitNorm& n, const float* g_next);
+  // the step parameter block: 8 bytes of seed, PAR_ROWS arrays of max_batch 4-byte entries, the per-row
+  // seeds (par_seeds_off_), the masks (par_mask_off_) -- finalize points the d_* members at the same offsets
+  enum { PAR_SLOT, PAR_TOKEN, PAR_POS, PAR_SEQLEN, PAR_TOPK, PAR_TEMP, PAR_TOPP, PAR_ROWS };
+  size_t par_off(int array) const { return 8 + (size_t)array * cfg_.max_batch * 4; }
+  size_t par_seeds_off_ = 0;
+  // a step's rows into the pinned block at hpar (tokens empty: that array is left alone)
+  void write_step_params(char* hpar, const std::vector<int>& slots, const std::vector<int>& tokens,
+                         const std::vector<int>& pos, const std::vector<float>& temperature,
+                         const std::vector<int>& top_k, const std::vector<float>& top_p, uint64_t seed,
+                         const std::vector<uint64_t>& seeds);
   void gemv(const std::vector<const QMat*>& segs, int N, int K, int B, const float* x, int ldx, const float* norm_w,
             float* y, int ldy, int epi, int layer);
   GemvArgs gemv_args(const std::vector<const QMat*>& segs, int N, int K, int B, const float* x, int ldx,
-                     const float* norm_w, float* y, int ldy, int epi, int layer);
+                     const float* norm_w, float* y, int ldy, int epi, int layer);  // gemv_base + the shape's knobs
+  GemvArgs gemv_base(const std::vector<const QMat*>& segs, int N, int K, int B, const float* x, int ldx,
+                     const float* norm_w, float* y, int ldy, int epi, int layer) const;
   QMat alloc_qmat(int qt, int rows, int cols);
   QMat upload_qmat(int qt, int rows, int cols, const void* host, size_t nbytes);
   // load-time staging: two device buffers (tensor i repacks while i+1 uploads) fed through two
@@ -486,7 +544,6 @@ class Engine {
   int nrm_parts_ = 0;  // tiles of the d_model-wide producer GEMM (0: fusion unavailable)
   bool nrm_on(int B) const;
   bool tpn_on(int B) const;  // batched TP decode: C1 / C2 fused with the next RMSNorm
- private:
   void layer_decode_gemm(int l, int B);
   hipGraphExec_t step_graph(int B);
   bool nrm_lm_ = false;  // the last layer's down GEMM prepared dec_xn16_ / nrm_part_ for lm_head(x_)
@@ -520,9 +577,7 @@ class Engine {
   // batched TP decode: the fused all-reduce's split-norm partials [max_batch][tpn_parts_] (0: off)
   int tpn_parts_ = 0;
   float* tpn_part_ = nullptr;
-  // the split-norm partials the lm_head consumes when nrm_lm_ is set (nrm_part_ or tpn_part_)
-  const float* lm_nrm_in_ = nullptr;
-  int lm_nrm_parts_ = 0;
+  SplitNorm lm_nrm_{};  // the split-norm operands the lm_head consumes when nrm_lm_ is set (nrm_part_ or tpn_part_)
   void* allgather_ctx_ = nullptr;
   // sampling config for the enqueued step
   bool sample_temp_ = false;

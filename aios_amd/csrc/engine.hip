@@ -541,8 +541,8 @@ void Engine::finalize() {
     // block: a scheduler decode() uploads all of them with a single async copy (round 1 issued 8
     // pageable copies per step)
     const size_t mb = (size_t)Bm * ((V + 7) / 8);
-    const size_t seeds_off = align_up(8 + (size_t)Bm * 4 * 7, 8);  // per-row seeds after the 7 row arrays
-    par_mask_off_ = align_up(seeds_off + (size_t)Bm * 8, 256);
+    par_seeds_off_ = align_up(par_off(PAR_ROWS), 8);  // per-row seeds after the row arrays
+    par_mask_off_ = align_up(par_seeds_off_ + (size_t)Bm * 8, 256);
     par_bytes_ = par_mask_off_ + mb;
     d_par_ = (char*)dmalloc(par_bytes_);
     ws += par_bytes_;
@@ -558,16 +558,16 @@ void Engine::finalize() {
     HIP_CHECK(hipHostMalloc((void**)&h_tok_out_, (size_t)Bm * 4, hipHostMallocDefault));
     std::memset(h_par_, 0, 2 * par_bytes_);
     d_seed_ = (uint64_t*)d_par_;
-    d_slot_ = (int*)(d_par_ + 8);
-    d_tokens_ = d_slot_ + Bm;
-    d_pos_ = d_tokens_ + Bm;
-    d_seqlen_ = d_pos_ + Bm;
-    d_topk_ = d_seqlen_ + Bm;
-    d_temp_ = (float*)(d_topk_ + Bm);
-    d_topp_ = d_temp_ + Bm;
-    d_seeds_ = (uint64_t*)(d_par_ + seeds_off);
+    d_slot_ = (int*)(d_par_ + par_off(PAR_SLOT));
+    d_tokens_ = (int*)(d_par_ + par_off(PAR_TOKEN));
+    d_pos_ = (int*)(d_par_ + par_off(PAR_POS));
+    d_seqlen_ = (int*)(d_par_ + par_off(PAR_SEQLEN));
+    d_topk_ = (int*)(d_par_ + par_off(PAR_TOPK));
+    d_temp_ = (float*)(d_par_ + par_off(PAR_TEMP));
+    d_topp_ = (float*)(d_par_ + par_off(PAR_TOPP));
+    d_seeds_ = (uint64_t*)(d_par_ + par_seeds_off_);
     d_mask_ = (uint8_t*)(d_par_ + par_mask_off_);
-    float* htp = (float*)(h_par_ + 8) + 6 * (size_t)Bm;
+    float* htp = (float*)(h_par_ + par_off(PAR_TOPP));
     for (int b = 0; b < Bm; ++b) htp[b] = 1.f;
     HIP_CHECK(hipMemcpy(d_par_, h_par_, par_bytes_, hipMemcpyHostToDevice));
   }
@@ -809,6 +809,13 @@ void Engine::gemv(const std::vector<const QMat*>& segs, int N, int K, int B, con
 
 GemvArgs Engine::gemv_args(const std::vector<const QMat*>& segs, int N, int K, int B, const float* x, int ldx,
                            const float* norm_w, float* y, int ldy, int epi, int layer) {
+  GemvArgs a = gemv_base(segs, N, K, B, x, ldx, norm_w, y, ldy, epi, layer);
+  apply_knobs(a, K == cfg_.d_ff ? "DOWN" : (N == 2 * cfg_.d_ff ? "GU" : (N == cfg_.vocab_size ? "LM" : "O")));
+  return a;
+}
+
+GemvArgs Engine::gemv_base(const std::vector<const QMat*>& segs, int N, int K, int B, const float* x, int ldx,
+                           const float* norm_w, float* y, int ldy, int epi, int layer) const {
   GemvArgs a;
   std::memset(&a, 0, sizeof(a));
   a.act_q8 = cfg_.act_q8;
@@ -845,7 +852,6 @@ GemvArgs Engine::gemv_args(const std::vector<const QMat*>& segs, int N, int K, i
     a.v_cache = kv_layer(v_cache_, layer);
     kv_write_args(a, layer);
   }
-  apply_knobs(a, K == cfg_.d_ff ? "DOWN" : (N == 2 * cfg_.d_ff ? "GU" : (N == cfg_.vocab_size ? "LM" : "O")));
   return a;
 }
 
@@ -865,8 +871,80 @@ void Engine::gemm(GemmQArgs& g) {
   launch_gemm_q(g, stream_);
 }
 
-// one transformer block for the B rows staged in x_ (decode) -- also used by prefill with
-// pointers swapped in (see prefill()).
+GemvArgs Engine::qkv_gemv_args(int l, const std::vector<const QMat*>& grp, int row0, int B, const float* x, bool fused,
+                               float* q, float* qkv, const int* pos, const int* slot) {
+  const int d = cfg_.d_model, qd = cfg_.n_heads * cfg_.head_dim, kvd = cfg_.n_kv_heads * cfg_.head_dim;
+  int n = 0;
+  for (auto* m : grp) n += m->w.rows;
+  GemvArgs a = gemv_base(grp, n, d, B, x, d, layers_[l].attn_norm, fused ? q : qkv, fused ? qd : qd + 2 * kvd,
+                         fused ? EPI_QKV : EPI_STORE, l);
+  a.row_base = row0;
+  if (fused) { a.pos = pos; a.slot = slot; a.block_table = d_bt_; }
+  return a;
+}
+
+QkvPostArgs Engine::qkv_post_args(int l, const float* qkv, int ldqkv, int T, const int* pos, const int* slot,
+                                  float* q_out, const float* bias, unsigned* amax) const {
+  const LayerW& L = layers_[l];
+  QkvPostArgs p;
+  p.qkv = qkv; p.ldqkv = ldqkv; p.T = T;
+  p.n_heads = cfg_.n_heads; p.n_kv_heads = cfg_.n_kv_heads; p.head_dim = cfg_.head_dim;
+  p.bias = bias; p.q_norm = L.q_norm; p.k_norm = L.k_norm; p.eps = cfg_.norm_eps;
+  p.rope_neox = cfg_.rope_neox; p.rope_base = cfg_.rope_theta; p.rope_cs = rope_cs_;
+  p.pos = pos; p.slot = slot; p.q_out = q_out;
+  p.k_cache = kv_layer(k_cache_, l); p.v_cache = kv_layer(v_cache_, l);
+  p.max_ctx = cfg_.max_ctx; p.block_table = d_bt_;
+  kv_write_args(p, l);
+  p.amax = amax;
+  return p;
+}
+
+AttnDecodeArgs Engine::attn_decode_args(int l, int B, const float* q, float* out, const int* seq_len, const int* slot,
+                                        const int* block_table, int bt_rows, float* o_part, float* ml,
+                                        bf16_t* out16) const {
+  AttnDecodeArgs a;
+  a.split = 0;
+  a.q = q; a.k_cache = kv_layer(k_cache_, l); a.v_cache = kv_layer(v_cache_, l);
+  kv_read_args(a, l);
+  a.seq_len = seq_len; a.slot = slot; a.block_table = block_table; a.bt_rows = bt_rows;
+  a.B = B; a.n_heads = cfg_.n_heads; a.n_kv_heads = cfg_.n_kv_heads; a.head_dim = cfg_.head_dim;
+  a.max_ctx = cfg_.max_ctx; a.n_chunks = n_chunks_; a.scale = 1.f / std::sqrt((float)cfg_.head_dim);
+  a.o_part = o_part; a.ml = ml; a.out = out; a.out16 = out16; a.counters = attn_cnt_;
+  return a;
+}
+
+GemmQArgs Engine::gemm_args(const bf16_t* A, int lda, int M, int K, const QWeight& w, int N, int ldc, float* C, int epi) {
+  GemmQArgs g;
+  std::memset(&g, 0, sizeof(g));
+  g.A = A; g.lda = lda; g.M = M; g.K = K; g.nseg = 1; g.seg[0] = w; g.N = N; g.C = C; g.ldc = ldc; g.epi = epi;
+  return g;
+}
+
+GemmQArgs Engine::qkv_gemm_args(int l, const bf16_t* A, int M, float* C) const {
+  const LayerW& L = layers_[l];
+  const int d = cfg_.d_model, qd = cfg_.n_heads * cfg_.head_dim, kvd = cfg_.n_kv_heads * cfg_.head_dim;
+  GemmQArgs g = gemm_args(A, d, M, d, L.wq.w, qd + 2 * kvd, qd + 2 * kvd, C, GEPI_STORE);
+  g.nseg = 3; g.seg[1] = L.wk.w; g.seg[2] = L.wv.w;
+  g.seg_n0[0] = 0; g.seg_n0[1] = qd; g.seg_n0[2] = qd + kvd;
+  return g;
+}
+void Engine::qkv_gemm_epi(GemmQArgs& g, int l, const int* pos, const int* slot, float* q_out) const {
+  g.epi = GEPI_QKV; g.col0 = 0;
+  g.head_dim = cfg_.head_dim; g.q_dim = cfg_.n_heads * cfg_.head_dim; g.kv_dim = cfg_.n_kv_heads * cfg_.head_dim;
+  g.n_kv_heads = cfg_.n_kv_heads; g.max_ctx = cfg_.max_ctx;
+  g.rope_cs = rope_cs_; g.pos = pos; g.slot = slot; g.block_table = d_bt_;
+  g.q_out = q_out; g.k_cache = kv_layer(k_cache_, l); g.v_cache = kv_layer(v_cache_, l);
+  kv_write_args(g, l);
+}
+
+void Engine::nrm_consume(GemmQArgs& g, const SplitNorm& n) const {
+  g.A = n.xn16; g.nrm_in = n.part; g.nrm_parts = n.parts; g.nrm_eps = cfg_.norm_eps;
+}
+void Engine::nrm_produce(GemmQArgs& g, const SplitNorm& n, const float* g_next) {
+  g.epi = GEPI_ACCUM_NORM; g.nrm_g = g_next; g.nrm_out16 = n.xn16; g.nrm_part = n.part; g.nrm_parts = n.parts;
+}
+
+// one transformer block for the B rows staged in x_ (decode).
 // Batched decode (B >= dec_gemm_min_b_): the int8 GEMV's dot work grows with B while the weight
 // stream does not, so from two concurrent sequences on the projections go through the skinny
 // MFMA GEMM (weights dequantised once per step into MFMA operands, split-K reduced in-launch),
@@ -881,40 +959,21 @@ bool Engine::tpn_on(int B) const {
 
 void Engine::layer_decode_gemm(int l, int B) {
   const LayerW& L = layers_[l];
-  const int d = cfg_.d_model, hd = cfg_.head_dim, H = cfg_.n_heads, Hkv = cfg_.n_kv_heads, ff = cfg_.d_ff;
-  const int qd = H * hd, kvd = Hkv * hd, ldqkv = qd + 2 * kvd;
+  const int d = cfg_.d_model, ff = cfg_.d_ff, qd = cfg_.n_heads * cfg_.head_dim;
+  const int ldqkv = qd + 2 * cfg_.n_kv_heads * cfg_.head_dim;
   const bool tp = cfg_.tp_size > 1;
   const bool fn = nrm_on(B);
   const bool tpn = tp && tpn_on(B);  // (fn and tpn are exclusive: fn needs tp_size 1)
-  bf16_t* kc = kv_layer(k_cache_, l);
-  bf16_t* vc = kv_layer(v_cache_, l);
-  // consumer side of the split RMSNorm: A = bf16(x * g) from the previous residual GEMM
-  auto nrm_in = [&](GemmQArgs& g) {
-    g.A = dec_xn16_; g.nrm_in = nrm_part_; g.nrm_parts = nrm_parts_; g.nrm_eps = cfg_.norm_eps;
-  };
-  // producer side: residual add + bf16(x_new * g_next) + per-tile sums of squares
-  auto nrm_out = [&](GemmQArgs& g, const float* g_next) {
-    g.epi = GEPI_ACCUM_NORM; g.nrm_g = g_next; g.nrm_out16 = dec_xn16_; g.nrm_part = nrm_part_;
-    g.nrm_parts = nrm_parts_;
-  };
-  // TP: the same contract, produced by the fused all-reduce (C1 / C2) into tpn_part_
-  auto tpn_in = [&](GemmQArgs& g) {
-    g.A = dec_xn16_; g.nrm_in = tpn_part_; g.nrm_parts = tpn_parts_; g.nrm_eps = cfg_.norm_eps;
-  };
+  // the split RMSNorm's operands: written by the residual GEMMs, or (TP) by the fused all-reduce (C1 / C2)
+  const SplitNorm sn = tpn ? SplitNorm{dec_xn16_, tpn_part_, tpn_parts_} : SplitNorm{dec_xn16_, nrm_part_, nrm_parts_};
   auto tp_reduce = [&](float* part, const float* g_next) {
     if (tpn) allreduce_norm_(allreduce_norm_ctx_, part, B, d, x_, ResidNorm{g_next, dec_xn16_, d, tpn_part_, tpn_parts_},
                              stream_);
     else allreduce(part, (size_t)B * d, x_);
   };
   if (!((fn || tpn) && l > 0)) launch_rmsnorm_bf16(x_, d, L.attn_norm, dec_a16_, d, B, d, cfg_.norm_eps, stream_);
-  GemmQArgs g;
-  std::memset(&g, 0, sizeof(g));
-  g.A = dec_a16_; g.lda = d; g.M = B; g.K = d; g.nseg = 3;
-  if (fn && l > 0) nrm_in(g);
-  if (tpn && l > 0) tpn_in(g);
-  g.seg[0] = L.wq.w; g.seg[1] = L.wk.w; g.seg[2] = L.wv.w;
-  g.seg_n0[0] = 0; g.seg_n0[1] = qd; g.seg_n0[2] = qd + kvd;
-  g.N = ldqkv; g.C = qkv_; g.ldc = ldqkv; g.epi = GEPI_STORE;
+  GemmQArgs g = qkv_gemm_args(l, dec_a16_, B, qkv_);
+  if ((fn || tpn) && l > 0) nrm_consume(g, sn);
   // RoPE + q store + KV-cache write in the GEMM epilogue (one launch per layer less) whenever
   // qkv_post would only do that (non-NeoX pairs, no QK-norm, no QKV bias)
   static const int qkv_epi_max_b = [] {
@@ -922,61 +981,30 @@ void Engine::layer_decode_gemm(int l, int B) {
     return e ? std::atoi(e) : 64;
   }();
   const bool qkv_epi = !cfg_.qk_norm && !cfg_.rope_neox && !L.bqkv && rope_cs_ && B <= qkv_epi_max_b;
-  if (qkv_epi) {
-    g.epi = GEPI_QKV; g.col0 = 0;
-    g.head_dim = hd; g.q_dim = qd; g.kv_dim = kvd; g.n_kv_heads = Hkv; g.max_ctx = cfg_.max_ctx;
-    g.rope_cs = rope_cs_; g.pos = d_pos_; g.slot = d_slot_; g.block_table = d_bt_;
-    g.q_out = q_; g.k_cache = kc; g.v_cache = vc;
-    kv_write_args(g, l);
-  }
+  if (qkv_epi) qkv_gemm_epi(g, l, d_pos_, d_slot_, q_);
   gemm(g);
   static const bool attn_out16 = !(std::getenv("AIOS_ATTN_OUT16") && std::atoi(std::getenv("AIOS_ATTN_OUT16")) == 0);
-  if (!qkv_epi) {
-  QkvPostArgs p;
-  p.qkv = qkv_; p.ldqkv = ldqkv; p.T = B;
-  p.n_heads = H; p.n_kv_heads = Hkv; p.head_dim = hd;
-  p.bias = L.bqkv; p.q_norm = L.q_norm; p.k_norm = L.k_norm; p.eps = cfg_.norm_eps;
-  p.rope_neox = cfg_.rope_neox; p.rope_base = cfg_.rope_theta; p.rope_cs = rope_cs_;
-  p.pos = d_pos_; p.slot = d_slot_; p.q_out = q_;
-  p.k_cache = kc; p.v_cache = vc; p.max_ctx = cfg_.max_ctx; p.block_table = d_bt_;
-  kv_write_args(p, l);
-  launch_qkv_post(p, stream_);
-  }
-  {
-    AttnDecodeArgs a;
-    a.split = 0;
-    a.q = q_; a.k_cache = kc; a.v_cache = vc; a.seq_len = d_seqlen_; a.slot = d_slot_;
-    kv_read_args(a, l);
-    a.block_table = attn_bt_; a.bt_rows = attn_bt_rows_;
-    a.B = B; a.n_heads = H; a.n_kv_heads = Hkv; a.head_dim = hd; a.max_ctx = cfg_.max_ctx;
-    a.n_chunks = n_chunks_; a.scale = 1.f / std::sqrt((float)hd);
-    a.o_part = opart_; a.ml = ml_; a.out = attn_; a.counters = attn_cnt_;
-    if (attn_out16) a.out16 = dec_a16_;  // bf16 straight from the attention epilogue (no conversion launch)
-    launch_attn_decode(a, stream_);
-  }
+  if (!qkv_epi) launch_qkv_post(qkv_post_args(l, qkv_, ldqkv, B, d_pos_, d_slot_, q_, L.bqkv, nullptr), stream_);
+  // (out16: bf16 straight from the attention epilogue, no conversion launch)
+  launch_attn_decode(attn_decode_args(l, B, q_, attn_, d_seqlen_, d_slot_, attn_bt_, attn_bt_rows_, opart_, ml_,
+                                      attn_out16 ? dec_a16_ : nullptr),
+                     stream_);
   if (!attn_out16) launch_f32_to_bf16(attn_, dec_a16_, (size_t)B * qd, stream_);
-  std::memset(&g, 0, sizeof(g));
-  g.A = dec_a16_; g.lda = qd; g.M = B; g.K = qd; g.nseg = 1; g.seg[0] = L.wo.w; g.N = d; g.ldc = d;
-  if (tp) { g.C = ff_; g.epi = GEPI_STORE; } else { g.C = x_; g.epi = GEPI_ACCUM; }
-  if (fn) nrm_out(g, L.ffn_norm);
+  g = gemm_args(dec_a16_, qd, B, qd, L.wo.w, d, d, tp ? ff_ : x_, tp ? GEPI_STORE : GEPI_ACCUM);
+  if (fn) nrm_produce(g, sn, L.ffn_norm);
   gemm(g);
   if (tp) tp_reduce(ff_, L.ffn_norm);
   if (!fn && !tpn) launch_rmsnorm_bf16(x_, d, L.ffn_norm, dec_a16_, d, B, d, cfg_.norm_eps, stream_);
-  std::memset(&g, 0, sizeof(g));
-  g.A = dec_a16_; g.lda = d; g.M = B; g.K = d; g.nseg = 1; g.seg[0] = L.wgu.w; g.N = 2 * ff;
-  g.C16 = dec_ff16_; g.ldc = ff; g.epi = GEPI_SWIGLU_BF16;
-  if (fn) nrm_in(g);
-  if (tpn) tpn_in(g);
+  g = gemm_args(dec_a16_, d, B, d, L.wgu.w, 2 * ff, ff, nullptr, GEPI_SWIGLU_BF16);
+  g.C16 = dec_ff16_;
+  if (fn || tpn) nrm_consume(g, sn);
   gemm(g);
-  std::memset(&g, 0, sizeof(g));
-  g.A = dec_ff16_; g.lda = ff; g.M = B; g.K = ff; g.nseg = 1; g.seg[0] = L.wdown.w; g.N = d; g.ldc = d;
-  if (tp) { g.C = attn_; g.epi = GEPI_STORE; } else { g.C = x_; g.epi = GEPI_ACCUM; }
+  g = gemm_args(dec_ff16_, ff, B, ff, L.wdown.w, d, d, tp ? attn_ : x_, tp ? GEPI_STORE : GEPI_ACCUM);
   // the next consumer: layer l + 1's QKV, or the lm_head after the last layer
   const float* g_next = l + 1 < cfg_.n_layers ? layers_[l + 1].attn_norm : out_norm_;
-  if (fn) nrm_out(g, g_next);
+  if (fn) nrm_produce(g, sn, g_next);
   nrm_lm_ = (fn || tpn) && l + 1 == cfg_.n_layers;
-  lm_nrm_in_ = tpn ? tpn_part_ : nrm_part_;
-  lm_nrm_parts_ = tpn ? tpn_parts_ : nrm_parts_;
+  lm_nrm_ = sn;
   gemm(g);
   if (tp) tp_reduce(attn_, g_next);
 }
@@ -990,80 +1018,28 @@ void Engine::layer_decode(int l, int B) {
   const LayerW& L = layers_[l];
   const int d = cfg_.d_model, hd = cfg_.head_dim, qd = cfg_.n_heads * hd, kvd = cfg_.n_kv_heads * hd;
   const bool fused_qkv = !cfg_.qk_norm && !cfg_.rope_neox;
-  auto qkv_args = [&](const std::vector<const QMat*>& grp, int row0) {
-    int n = 0;
-    for (auto* m : grp) n += m->w.rows;
-    GemvArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.act_q8 = cfg_.act_q8;
-    a.nseg = (int)grp.size();
-    int r = 0;
-    for (int s = 0; s < a.nseg; ++s) { a.seg[s] = grp[s]->w; a.seg_row0[s] = r; r += grp[s]->w.rows; }
-    a.N = n; a.K = d; a.B = B; a.row_base = row0;
-    a.x = x_; a.ldx = d; a.norm_w = L.attn_norm; a.eps = cfg_.norm_eps;
-    if (fused_qkv) {
-      a.epi = EPI_QKV; a.y = q_; a.ldy = qd;
-      a.bias = L.bqkv;
-      a.head_dim = hd; a.q_dim = qd; a.kv_dim = kvd; a.n_kv_heads = cfg_.n_kv_heads; a.max_ctx = cfg_.max_ctx;
-      a.rope_neox = cfg_.rope_neox; a.rope_base = cfg_.rope_theta; a.rope_cs = rope_cs_;
-      a.pos = d_pos_; a.slot = d_slot_;
-      a.k_cache = kv_layer(k_cache_, l);
-      a.v_cache = kv_layer(v_cache_, l);
-      kv_write_args(a, l);
-      a.block_table = d_bt_;
-      if (step_prep_on_ && B == 1) { a.step_kv = d_step_kv_; a.step_rope = d_step_rope_; }
-    } else {
-      a.epi = EPI_STORE; a.y = qkv_; a.ldy = qd + 2 * kvd;
-    }
-    apply_knobs(a, "QKV");
-    static const int qkv_dbg = [] {  // probes only (AIOS_QKV_DBG=0x20000: epilogue lookups skipped)
-      const char* e = std::getenv("AIOS_QKV_DBG");
-      return e ? (int)std::strtol(e, nullptr, 0) : 0;
-    }();
-    a.tune_dbg = qkv_dbg;
-    return a;
-  };
   // ---- QKV (+RMSNorm prologue, RoPE + KV-cache epilogue)
   {
     int row0 = 0;
     for (auto& grp : qkv_groups(L)) {
-      const GemvArgs a = qkv_args(grp, row0);
+      GemvArgs a = qkv_gemv_args(l, grp, row0, B, x_, fused_qkv, q_, qkv_, d_pos_, d_slot_);
+      if (fused_qkv && step_prep_on_ && B == 1) { a.step_kv = d_step_kv_; a.step_rope = d_step_rope_; }
+      apply_knobs(a, "QKV");
+      static const int qkv_dbg = [] {  // probes only (AIOS_QKV_DBG=0x20000: epilogue lookups skipped)
+        const char* e = std::getenv("AIOS_QKV_DBG");
+        return e ? (int)std::strtol(e, nullptr, 0) : 0;
+      }();
+      a.tune_dbg = qkv_dbg;
       launch_gemv(a, stream_);
       row0 += a.N;
     }
     if (!fused_qkv) {
       if (L.bqkv) throw std::runtime_error("qkv bias with unfused QKV path not supported yet");
-      QkvPostArgs p;
-      p.qkv = qkv_; p.ldqkv = qd + 2 * kvd; p.T = B;
-      p.n_heads = cfg_.n_heads; p.n_kv_heads = cfg_.n_kv_heads; p.head_dim = hd;
-      p.q_norm = L.q_norm; p.k_norm = L.k_norm; p.eps = cfg_.norm_eps;
-      p.rope_neox = cfg_.rope_neox; p.rope_base = cfg_.rope_theta; p.rope_cs = rope_cs_;
-      p.pos = d_pos_; p.slot = d_slot_; p.q_out = q_;
-      p.k_cache = kv_layer(k_cache_, l);
-      p.v_cache = kv_layer(v_cache_, l);
-      kv_write_args(p, l);
-      p.max_ctx = cfg_.max_ctx;
-      p.block_table = d_bt_;
-      launch_qkv_post(p, stream_);
+      launch_qkv_post(qkv_post_args(l, qkv_, qd + 2 * kvd, B, d_pos_, d_slot_, q_, nullptr, nullptr), stream_);
     }
   }
   // ---- attention (fp32 output: a bf16 hand-off to O measured neutral, 544.0-544.5 vs 545.0-545.7 tok/s)
-  {
-    AttnDecodeArgs a;
-    a.split = 0;
-    a.q = q_;
-    a.k_cache = kv_layer(k_cache_, l);
-    a.v_cache = kv_layer(v_cache_, l);
-    kv_read_args(a, l);
-    a.seq_len = d_seqlen_;
-    a.slot = d_slot_;
-    a.block_table = attn_bt_; a.bt_rows = attn_bt_rows_;
-    a.B = B; a.n_heads = cfg_.n_heads; a.n_kv_heads = cfg_.n_kv_heads; a.head_dim = hd; a.max_ctx = cfg_.max_ctx;
-    a.n_chunks = n_chunks_;
-    a.scale = 1.f / std::sqrt((float)hd);
-    a.o_part = opart_; a.ml = ml_; a.out = attn_; a.counters = attn_cnt_;
-    launch_attn_decode(a, stream_);
-  }
+  launch_attn_decode(attn_decode_args(l, B, q_, attn_, d_seqlen_, d_slot_, attn_bt_, attn_bt_rows_, opart_, ml_), stream_);
   // ---- O projection (+ residual; TP: partial -> all-reduce -> add, fused into the GEMV epilogue
   // when the comm provides it)
   {
@@ -1152,11 +1128,8 @@ void Engine::lm_head(int B, const float* x, int ldx) {
     const bool fused = nrm_lm_ && x == x_ && ldx == d;  // normalised by the last down GEMM
     nrm_lm_ = false;  // one use: a later lm_head (prefill) normalises for itself
     if (!fused) launch_rmsnorm_bf16(x, ldx, out_norm_, dec_a16_, d, B, d, cfg_.norm_eps, stream_);
-    GemmQArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.A = dec_a16_; g.lda = d; g.M = B; g.K = d; g.nseg = 1; g.seg[0] = output_.w; g.N = Vl;
-    g.C = y; g.ldc = V; g.epi = GEPI_STORE;
-    if (fused) { g.A = dec_xn16_; g.nrm_in = lm_nrm_in_; g.nrm_parts = lm_nrm_parts_; g.nrm_eps = cfg_.norm_eps; }
+    GemmQArgs g = gemm_args(dec_a16_, d, B, d, output_.w, Vl, V, y, GEPI_STORE);
+    if (fused) nrm_consume(g, lm_nrm_);
     gemm(g);
   } else {
     gemv({&output_}, Vl, d, B, x, ldx, out_norm_, y, V, EPI_STORE, 0);
@@ -1289,20 +1262,24 @@ Engine::Logprobs Engine::last_logprobs() const {
   return r;
 }
 
-void Engine::enqueue_sample(int B, bool processors) {
-  const int V = cfg_.vocab_size;
+SampleArgs Engine::sample_args(int B, bool masked) const {
   SampleArgs s;
   std::memset(&s, 0, sizeof(s));
-  s.logits = logits_; s.ldl = V; s.B = B; s.V = V;
-  s.temperature = d_temp_; s.top_k = d_topk_;
+  s.logits = logits_; s.ldl = cfg_.vocab_size; s.B = B; s.V = cfg_.vocab_size;
+  s.temperature = d_temp_; s.top_k = d_topk_; s.top_p = d_topp_; s.seeds = d_seeds_;
+  s.tokens = d_tokens_;
+  s.mask = masked ? d_mask_ : nullptr;
+  s.ws = sample_ws_; s.ws_bytes = sample_ws_bytes_; s.counters = sample_cnt_;
+  return s;
+}
+
+void Engine::enqueue_sample(int B, bool processors) {
+  SampleArgs s = sample_args(B, sample_mask_);
   s.seed = sample_seed_;
   s.seed_dev = d_seed_;
-  s.seeds = d_seeds_;
-  s.tokens = d_tokens_; s.pos = d_pos_; s.seq_len = d_seqlen_;
+  s.pos = d_pos_; s.seq_len = d_seqlen_;
   s.history = d_history_; s.hist_stride = cfg_.max_ctx + 1;
   s.advance = 1;
-  s.mask = sample_mask_ ? d_mask_ : nullptr;
-  s.top_p = d_topp_; s.ws = sample_ws_; s.ws_bytes = sample_ws_bytes_; s.counters = sample_cnt_;
   if (processors) take_processors(s, B);
   launch_sample(s, stream_);
 }
@@ -1316,12 +1293,13 @@ bool Engine::gemm_prefill_ok(int T) const { return gm_ok_ && T >= gm_min_rows_; 
 // so every weight byte is dequantised once per chunk (not once per 8 rows as on the GEMV path).
 // TP: the row-parallel O / down outputs go through the all-reduce hook into the residual.
 void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
-                          const EmbedFold* fold, const ScoreFold* score) {
+                          const ChunkHook& hook) {
   TraceRange tr("aios.prefill_gemm");
   const int T = (int)tokens.size();
   const int d = cfg_.d_model, hd = cfg_.head_dim, H = cfg_.n_heads, Hkv = cfg_.n_kv_heads, ff = cfg_.d_ff;
-  const int qd = H * hd, kvd = Hkv * hd, ldqkv = qd + 2 * kvd, V = cfg_.vocab_size;
+  const int qd = H * hd, ldqkv = qd + 2 * Hkv * hd;
   const bool tp = cfg_.tp_size > 1;
+  const SplitNorm sn{gm_xn16_, gm_npart_, gm_nparts_};  // (as in layer_decode_gemm, on a short chunk's rows)
   std::vector<int> hp(gm_rows_), hs(gm_rows_, slot);
   // short chunks (n <= max_batch, the batched-decode GEMMs' shapes): the decode step's fusions --
   // RoPE + KV write in the QKV GEMM's epilogue and the split RMSNorm (the residual GEMMs write
@@ -1335,9 +1313,9 @@ void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_po
     const bool fnp = sh && gm_nparts_ > 0;
     // The prefill GEMM's split-K and stream-K plans add their partial tiles with fp32 atomics, in arrival
     // order, so two prefills of one prompt differ in the low bits (up to 9e-05 on the pooled unit vector
-    // of a bf16 model).  An embedding's chunks that reach it (more than 32 rows) ask for its best plan
-    // without them (ksplit < 0), so the same tokens pool to the same bytes; prefill() keeps its plans.
-    const bool no_split = fold && n > 32;
+    // of a bf16 model).  A deterministic call's chunks that reach it (more than 32 rows) ask for its best
+    // plan without them (ksplit < 0), so the same tokens pool to the same bytes; prefill() keeps its plans.
+    const bool no_split = hook.deterministic && n > 32;
     auto run = [&](GemmQArgs& g) {
       if (no_split) g.ksplit = -1;
       gemm(g);
@@ -1349,25 +1327,9 @@ void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_po
     launch_get_rows(tok_embd_.w, gm_tokens_, n, gm_x_, d, 1.f, stream_);
     for (int l = 0; l < cfg_.n_layers; ++l) {
       const LayerW& L = layers_[l];
-      bf16_t* kc = kv_layer(k_cache_, l);
-      bf16_t* vc = kv_layer(v_cache_, l);
-      // split-RMSNorm consumer / producer (as in layer_decode_gemm, on this chunk's rows)
-      auto nrm_in = [&](GemmQArgs& g) {
-        g.A = gm_xn16_; g.nrm_in = gm_npart_; g.nrm_parts = gm_nparts_; g.nrm_eps = cfg_.norm_eps;
-      };
-      auto nrm_out = [&](GemmQArgs& g, const float* g_next) {
-        g.epi = GEPI_ACCUM_NORM; g.nrm_g = g_next; g.nrm_out16 = gm_xn16_; g.nrm_part = gm_npart_;
-        g.nrm_parts = gm_nparts_;
-      };
       if (!(fnp && l > 0)) launch_rmsnorm_bf16(gm_x_, d, L.attn_norm, gm_a16_, d, n, d, cfg_.norm_eps, stream_);
-      GemmQArgs g;
-      std::memset(&g, 0, sizeof(g));
-      g.A = gm_a16_; g.lda = d; g.M = n; g.K = d;
-      if (fnp && l > 0) nrm_in(g);
-      g.nseg = 3;
-      g.seg[0] = L.wq.w; g.seg[1] = L.wk.w; g.seg[2] = L.wv.w;
-      g.seg_n0[0] = 0; g.seg_n0[1] = qd; g.seg_n0[2] = qd + kvd;
-      g.N = ldqkv; g.C = gm_qkv_; g.ldc = ldqkv; g.epi = GEPI_STORE;
+      GemmQArgs g = qkv_gemm_args(l, gm_a16_, n, gm_qkv_);
+      if (fnp && l > 0) nrm_consume(g, sn);
       // the RoPE / KV-cache epilogue: short chunks (ring / skinny GEMMs); the prefill GEMM's chunks
       // (>= 33 rows) only with AIOS_PREFILL_QKV_EPI=1 -- it needs S = 1 plans, and at 2048 tokens
       // the QKV GEMM then took 212.7 us against 115.7 (split-K) + 32 us of qkv_post (64 tokens:
@@ -1377,30 +1339,16 @@ void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_po
       bool qepi = false;
       if (qepi_ok) {
         GemmQArgs q = g;
-        q.epi = GEPI_QKV; q.col0 = 0;
-        q.head_dim = hd; q.q_dim = qd; q.kv_dim = kvd; q.n_kv_heads = Hkv; q.max_ctx = cfg_.max_ctx;
-        q.rope_cs = rope_cs_; q.pos = gm_pos_; q.slot = gm_slot_; q.block_table = d_bt_;
-        q.q_out = gm_q_; q.k_cache = kc; q.v_cache = vc;
-        kv_write_args(q, l);
+        qkv_gemm_epi(q, l, gm_pos_, gm_slot_, gm_q_);
         static const int pf_qkv = [] { const char* e = std::getenv("AIOS_PREFILL_QKV_EPI"); return e ? std::atoi(e) : 0; }();
         qepi = sh || (pf_qkv && gemm_pf_serves(q));
         if (qepi) g = q;
       }
       run(g);
-      if (!qepi) {
-      QkvPostArgs p;
-      p.qkv = gm_qkv_; p.ldqkv = ldqkv; p.T = n;
-      p.n_heads = H; p.n_kv_heads = Hkv; p.head_dim = hd;
-      p.bias = L.bqkv; p.q_norm = L.q_norm; p.k_norm = L.k_norm; p.eps = cfg_.norm_eps;
-      p.rope_neox = cfg_.rope_neox; p.rope_base = cfg_.rope_theta; p.rope_cs = rope_cs_;
-      p.pos = gm_pos_; p.slot = gm_slot_; p.q_out = gm_q_;
-      p.k_cache = kc; p.v_cache = vc; p.max_ctx = cfg_.max_ctx; p.block_table = d_bt_;
-      kv_write_args(p, l);
-      p.amax = kv_obs_table(l);
-      launch_qkv_post(p, stream_);
-      }
+      if (!qepi)
+        launch_qkv_post(qkv_post_args(l, gm_qkv_, ldqkv, n, gm_pos_, gm_slot_, gm_q_, L.bqkv, kv_obs_table(l)), stream_);
       AttnPrefillArgs at;
-      at.q = gm_q_; at.k_cache = kc; at.v_cache = vc; at.block_table = d_bt_;
+      at.q = gm_q_; at.k_cache = kv_layer(k_cache_, l); at.v_cache = kv_layer(v_cache_, l); at.block_table = d_bt_;
       kv_read_args(at, l);
       at.slot = slot; at.start = start_pos + r0; at.T = n;
       at.n_heads = H; at.n_kv_heads = Hkv; at.head_dim = hd; at.max_ctx = cfg_.max_ctx;
@@ -1408,38 +1356,99 @@ void Engine::prefill_gemm(int slot, const std::vector<int>& tokens, int start_po
       at.out = gm_attn16_; at.ldo = qd;
       launch_attn_prefill(at, stream_);
       // O projection (+ residual)
-      std::memset(&g, 0, sizeof(g));
-      g.A = gm_attn16_; g.lda = qd; g.M = n; g.K = qd; g.nseg = 1; g.seg[0] = L.wo.w; g.N = d; g.ldc = d;
-      if (tp) { g.C = gm_part_; g.epi = GEPI_STORE; } else { g.C = gm_x_; g.epi = GEPI_ACCUM; }
-      if (fnp) nrm_out(g, L.ffn_norm);
+      g = gemm_args(gm_attn16_, qd, n, qd, L.wo.w, d, d, tp ? gm_part_ : gm_x_, tp ? GEPI_STORE : GEPI_ACCUM);
+      if (fnp) nrm_produce(g, sn, L.ffn_norm);
       run(g);
       if (tp) allreduce(gm_part_, (size_t)n * d, gm_x_);
       // FFN
       if (!fnp) launch_rmsnorm_bf16(gm_x_, d, L.ffn_norm, gm_a16_, d, n, d, cfg_.norm_eps, stream_);
-      std::memset(&g, 0, sizeof(g));
-      g.A = gm_a16_; g.lda = d; g.M = n; g.K = d; g.nseg = 1; g.seg[0] = L.wgu.w; g.N = 2 * ff;
-      g.C16 = gm_ff16_; g.ldc = ff; g.epi = GEPI_SWIGLU_BF16;
-      if (fnp) nrm_in(g);
+      g = gemm_args(gm_a16_, d, n, d, L.wgu.w, 2 * ff, ff, nullptr, GEPI_SWIGLU_BF16);
+      g.C16 = gm_ff16_;
+      if (fnp) nrm_consume(g, sn);
       run(g);
-      std::memset(&g, 0, sizeof(g));
-      g.A = gm_ff16_; g.lda = ff; g.M = n; g.K = ff; g.nseg = 1; g.seg[0] = L.wdown.w; g.N = d; g.ldc = d;
-      if (tp) { g.C = gm_part_; g.epi = GEPI_STORE; } else { g.C = gm_x_; g.epi = GEPI_ACCUM; }
-      if (fnp && l + 1 < cfg_.n_layers) nrm_out(g, layers_[l + 1].attn_norm);  // (lm_head normalises its row)
+      g = gemm_args(gm_ff16_, ff, n, ff, L.wdown.w, d, d, tp ? gm_part_ : gm_x_, tp ? GEPI_STORE : GEPI_ACCUM);
+      if (fnp && l + 1 < cfg_.n_layers) nrm_produce(g, sn, layers_[l + 1].attn_norm);  // (lm_head normalises its row)
       run(g);
       if (tp) allreduce(gm_part_, (size_t)n * d, gm_x_);
     }
     if (r0 + n == T && want_logits) lm_head(1, gm_x_ + (size_t)(n - 1) * d, d);
-    if (fold) embed_fold(*fold, gm_x_, n, start_pos + r0, r0 + n == T);
-    if (score) score_fold(*score, gm_x_, n, r0);
+    if (hook.fn) hook.fn(gm_x_, n, r0, r0 + n == T);
+  }
+}
+
+// Prefill through the GEMVs: chunks of prefill_rows_ rows, per layer the projections in sub-batches of <= 8
+// rows and the decode attention once over the chunk's rows (causal by per-row seq_len).  Works on the pf_*
+// buffers through local pointers: the decode workspace (x_, q_, ..., d_pos_) is neither read nor written.
+// The decode step's extras stay off here: no QKV knobs / step-prep lookups, no bf16 SwiGLU hand-off, no
+// fused TP all-reduce epilogue.
+void Engine::prefill_gemv(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
+                          const ChunkHook& hook) {
+  const int T = (int)tokens.size(), R = prefill_rows_;
+  const int d = cfg_.d_model, ff = cfg_.d_ff, qd = cfg_.n_heads * cfg_.head_dim, kvd = cfg_.n_kv_heads * cfg_.head_dim;
+  const int ldqkv = qd + 2 * kvd;
+  const bool tp = cfg_.tp_size > 1;
+  // (calibration: EPI_STORE + qkv_post, where the observer sits)
+  const bool fused_qkv = !cfg_.qk_norm && !cfg_.rope_neox && !kv_obs_;
+  std::vector<int> hp(R), hs(R, slot), hsl(R);
+  for (int r0 = 0; r0 < T; r0 += R) {
+    const int n = std::min(R, T - r0);
+    for (int i = 0; i < n; ++i) { hp[i] = start_pos + r0 + i; hsl[i] = hp[i] + 1; }
+    HIP_CHECK(hipMemcpyAsync(pf_tokens_, tokens.data() + r0, n * 4, hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(pf_pos_, hp.data(), n * 4, hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(pf_seqlen_, hsl.data(), n * 4, hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(pf_slot_, hs.data(), n * 4, hipMemcpyHostToDevice, stream_));
+    launch_get_rows(tok_embd_.w, pf_tokens_, n, pf_x_, d, 1.f, stream_);
+    for (int l = 0; l < cfg_.n_layers; ++l) {
+      const LayerW& L = layers_[l];
+      // every projection: sub-batches of <= 8 rows, rows [o, o + bn) of the chunk
+      auto each_sub = [&](auto&& body) {
+        for (int o = 0; o < n; o += 8) body(o, std::min(8, n - o));
+      };
+      each_sub([&](int o, int bn) {
+        float *x = pf_x_ + (size_t)o * d, *q = pf_q_ + (size_t)o * qd, *qkv = pf_qkv_ + (size_t)o * ldqkv;
+        const int *pos = pf_pos_ + o, *slt = pf_slot_ + o;
+        int row0 = 0;
+        for (auto& grp : qkv_groups(L)) {
+          const GemvArgs a = qkv_gemv_args(l, grp, row0, bn, x, fused_qkv, q, qkv, pos, slt);
+          launch_gemv(a, stream_);
+          row0 += a.N;
+        }
+        // (bias and observer only while calibrating, in place of the fused epilogue's bias)
+        if (!fused_qkv)
+          launch_qkv_post(qkv_post_args(l, qkv, ldqkv, bn, pos, slt, q, kv_obs_ ? L.bqkv : nullptr, kv_obs_table(l)),
+                          stream_);
+      });
+      // attention for all n rows: one slot, the slot-indexed table
+      launch_attn_decode(attn_decode_args(l, n, pf_q_, pf_attn_, pf_seqlen_, pf_slot_, d_bt_, 0, pf_opart_, pf_ml_),
+                         stream_);
+      // O (+ residual; TP: partials into pf_ff_, all-reduced into the residual)
+      each_sub([&](int o, int bn) {
+        gemv({&L.wo}, d, qd, bn, pf_attn_ + (size_t)o * qd, qd, nullptr, (tp ? pf_ff_ : pf_x_) + (size_t)o * d, d,
+             tp ? EPI_STORE : EPI_RESID, l);
+      });
+      if (tp) allreduce(pf_ff_, (size_t)n * d, pf_x_);
+      each_sub([&](int o, int bn) {
+        gemv({&L.wgu}, 2 * ff, d, bn, pf_x_ + (size_t)o * d, d, L.ffn_norm, pf_ff_ + (size_t)o * ff, ff, EPI_SWIGLU, l);
+      });
+      // down (+ residual; TP: partials into pf_attn_)
+      each_sub([&](int o, int bn) {
+        gemv({&L.wdown}, d, ff, bn, pf_ff_ + (size_t)o * ff, ff, nullptr, (tp ? pf_attn_ : pf_x_) + (size_t)o * d, d,
+             tp ? EPI_STORE : EPI_RESID, l);
+      });
+      if (tp) allreduce(pf_attn_, (size_t)n * d, pf_x_);
+    }
+    // (lm_head normalises the row itself: x is not x_, and nrm_lm_ is false outside a decode step)
+    if (r0 + n == T && want_logits) lm_head(1, pf_x_ + (size_t)(n - 1) * d, d);
+    if (hook.fn) hook.fn(pf_x_, n, r0, r0 + n == T);
   }
 }
 
 std::vector<float> Engine::prefill(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits) {
-  return prefill_run(slot, tokens, start_pos, want_logits, nullptr);
+  return prefill_run(slot, tokens, start_pos, want_logits, ChunkHook{});
 }
 
 std::vector<float> Engine::prefill_run(int slot, const std::vector<int>& tokens, int start_pos, bool want_logits,
-                                       const EmbedFold* fold, const ScoreFold* score) {
+                                       const ChunkHook& hook) {
   const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
   TraceRange tr("aios.prefill");
   if (!finalized_) throw std::runtime_error("engine not finalized");
@@ -1452,160 +1461,12 @@ std::vector<float> Engine::prefill_run(int slot, const std::vector<int>& tokens,
     if (t < 0 || t >= cfg_.vocab_size) throw std::runtime_error("prefill: token id out of range");
   kv_prepare_write(slot, start_pos, start_pos + T);
   kv_sync(0);
-  if (gemm_prefill_ok(T)) {
-    prefill_gemm(slot, tokens, start_pos, want_logits, fold, score);
-    std::vector<float> out;
-    if (want_logits) {
-      out.resize(cfg_.vocab_size);
-      HIP_CHECK(hipMemcpyAsync(out.data(), logits_, (size_t)cfg_.vocab_size * 4, hipMemcpyDeviceToHost, stream_));
-    }
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    return out;
-  }
-  const int d = cfg_.d_model, V = cfg_.vocab_size;
-  const int R = prefill_rows_;
-  // swap decode workspace pointers with the prefill ones for the duration of the call
-  std::swap(x_, pf_x_); std::swap(q_, pf_q_); std::swap(qkv_, pf_qkv_); std::swap(attn_, pf_attn_);
-  std::swap(ff_, pf_ff_); std::swap(opart_, pf_opart_); std::swap(ml_, pf_ml_);
-  int* save_tok = d_tokens_; int* save_pos = d_pos_; int* save_sl = d_seqlen_; int* save_slot = d_slot_;
-  std::vector<int> hp(R), hs(R), hsl(R);
-  try {
-    for (int r0 = 0; r0 < T; r0 += R) {
-      const int n = std::min(R, T - r0);
-      for (int i = 0; i < n; ++i) { hp[i] = start_pos + r0 + i; hsl[i] = hp[i] + 1; hs[i] = slot; }
-      HIP_CHECK(hipMemcpyAsync(pf_tokens_, tokens.data() + r0, n * 4, hipMemcpyHostToDevice, stream_));
-      HIP_CHECK(hipMemcpyAsync(pf_pos_, hp.data(), n * 4, hipMemcpyHostToDevice, stream_));
-      HIP_CHECK(hipMemcpyAsync(pf_seqlen_, hsl.data(), n * 4, hipMemcpyHostToDevice, stream_));
-      HIP_CHECK(hipMemcpyAsync(pf_slot_, hs.data(), n * 4, hipMemcpyHostToDevice, stream_));
-      launch_get_rows(tok_embd_.w, pf_tokens_, n, x_, d, 1.f, stream_);
-      float* xb = x_;
-      float *qb = q_, *qkvb = qkv_, *ab = attn_, *fb = ff_;
-      for (int l = 0; l < cfg_.n_layers; ++l) {
-        // sub-batches of <= 8 rows through the GEMV path; attention over all n rows at once
-        const int nsub = (n + 7) / 8;
-        for (int sb = 0; sb < nsub; ++sb) {
-          const int o = sb * 8, bn = std::min(8, n - o);
-          x_ = xb + (size_t)o * d; q_ = qb + (size_t)o * cfg_.n_heads * cfg_.head_dim;
-          qkv_ = qkvb + (size_t)o * (cfg_.n_heads + 2 * cfg_.n_kv_heads) * cfg_.head_dim;
-          d_pos_ = pf_pos_ + o; d_slot_ = pf_slot_ + o; d_seqlen_ = pf_seqlen_ + o;
-          // QKV only (layer_decode runs the whole block; split it by temporarily faking)
-          const LayerW& L = layers_[l];
-          const int hd = cfg_.head_dim, qd = cfg_.n_heads * hd, kvd = cfg_.n_kv_heads * hd;
-          // (calibration: EPI_STORE + qkv_post, where the observer sits)
-          const bool fused_qkv = !cfg_.qk_norm && !cfg_.rope_neox && !kv_obs_;
-          int row0 = 0;
-          for (auto& grp : qkv_groups(L)) {
-            int nn = 0;
-            for (auto* m : grp) nn += m->w.rows;
-            GemvArgs a;
-            std::memset(&a, 0, sizeof(a));
-  a.act_q8 = cfg_.act_q8;
-            a.nseg = (int)grp.size();
-            int r = 0;
-            for (int s = 0; s < a.nseg; ++s) { a.seg[s] = grp[s]->w; a.seg_row0[s] = r; r += grp[s]->w.rows; }
-            a.N = nn; a.K = d; a.B = bn; a.row_base = row0;
-            a.x = x_; a.ldx = d; a.norm_w = L.attn_norm; a.eps = cfg_.norm_eps;
-            if (fused_qkv) {
-              a.epi = EPI_QKV; a.y = q_; a.ldy = qd; a.bias = L.bqkv;
-              a.head_dim = hd; a.q_dim = qd; a.kv_dim = kvd; a.n_kv_heads = cfg_.n_kv_heads; a.max_ctx = cfg_.max_ctx;
-              a.rope_neox = cfg_.rope_neox; a.rope_base = cfg_.rope_theta; a.rope_cs = rope_cs_;
-              a.pos = d_pos_; a.slot = d_slot_;
-              a.k_cache = kv_layer(k_cache_, l);
-              a.v_cache = kv_layer(v_cache_, l);
-              kv_write_args(a, l);
-              a.block_table = d_bt_;
-            } else {
-              a.epi = EPI_STORE; a.y = qkv_; a.ldy = qd + 2 * kvd;
-            }
-            launch_gemv(a, stream_);
-            row0 += nn;
-          }
-          if (!fused_qkv) {
-            QkvPostArgs p;
-            p.qkv = qkv_; p.ldqkv = qd + 2 * kvd; p.T = bn;
-            p.n_heads = cfg_.n_heads; p.n_kv_heads = cfg_.n_kv_heads; p.head_dim = hd;
-            p.q_norm = L.q_norm; p.k_norm = L.k_norm; p.eps = cfg_.norm_eps;
-            p.rope_neox = cfg_.rope_neox; p.rope_base = cfg_.rope_theta; p.rope_cs = rope_cs_;
-            p.pos = d_pos_; p.slot = d_slot_; p.q_out = q_;
-            p.k_cache = kv_layer(k_cache_, l);
-            p.v_cache = kv_layer(v_cache_, l);
-            kv_write_args(p, l);
-            p.max_ctx = cfg_.max_ctx;
-            p.block_table = d_bt_;
-            if (kv_obs_) { p.bias = L.bqkv; p.amax = kv_obs_table(l); }  // (the fused epilogue's bias)
-            launch_qkv_post(p, stream_);
-          }
-        }
-        // attention for all n rows (causal by per-row seq_len)
-        {
-          AttnDecodeArgs a;
-          a.split = 0;
-          a.q = qb;
-          a.k_cache = kv_layer(k_cache_, l);
-          a.v_cache = kv_layer(v_cache_, l);
-          kv_read_args(a, l);
-          a.seq_len = pf_seqlen_; a.slot = pf_slot_;
-          a.block_table = d_bt_; a.bt_rows = 0;  // prefill rows: one slot, slot-indexed table
-          a.B = n; a.n_heads = cfg_.n_heads; a.n_kv_heads = cfg_.n_kv_heads; a.head_dim = cfg_.head_dim;
-          a.max_ctx = cfg_.max_ctx;
-          a.n_chunks = n_chunks_;
-          a.scale = 1.f / std::sqrt((float)cfg_.head_dim);
-          a.o_part = opart_; a.ml = ml_; a.out = ab; a.counters = attn_cnt_;
-          launch_attn_decode(a, stream_);
-        }
-        for (int sb = 0; sb < nsub; ++sb) {
-          const int o = sb * 8, bn = std::min(8, n - o);
-          const LayerW& L = layers_[l];
-          const int qd = cfg_.n_heads * cfg_.head_dim;
-          float* xr = xb + (size_t)o * d;
-          if (cfg_.tp_size > 1) {
-            gemv({&L.wo}, d, qd, bn, ab + (size_t)o * qd, qd, nullptr, fb + (size_t)o * d, d, EPI_STORE, l);
-          } else {
-            gemv({&L.wo}, d, qd, bn, ab + (size_t)o * qd, qd, nullptr, xr, d, EPI_RESID, l);
-          }
-        }
-        if (cfg_.tp_size > 1) {
-          allreduce(fb, (size_t)n * d, xb);
-        }
-        for (int sb = 0; sb < nsub; ++sb) {
-          const int o = sb * 8, bn = std::min(8, n - o);
-          const LayerW& L = layers_[l];
-          gemv({&L.wgu}, 2 * cfg_.d_ff, d, bn, xb + (size_t)o * d, d, L.ffn_norm, fb + (size_t)o * cfg_.d_ff,
-               cfg_.d_ff, EPI_SWIGLU, l);
-        }
-        for (int sb = 0; sb < nsub; ++sb) {
-          const int o = sb * 8, bn = std::min(8, n - o);
-          const LayerW& L = layers_[l];
-          if (cfg_.tp_size > 1) {
-            gemv({&L.wdown}, d, cfg_.d_ff, bn, fb + (size_t)o * cfg_.d_ff, cfg_.d_ff, nullptr, ab + (size_t)o * d,
-                 d, EPI_STORE, l);
-          } else {
-            gemv({&L.wdown}, d, cfg_.d_ff, bn, fb + (size_t)o * cfg_.d_ff, cfg_.d_ff, nullptr, xb + (size_t)o * d,
-                 d, EPI_RESID, l);
-          }
-        }
-        if (cfg_.tp_size > 1) {
-          allreduce(ab, (size_t)n * d, xb);
-        }
-      }
-      x_ = xb; q_ = qb; qkv_ = qkvb; attn_ = ab; ff_ = fb;
-      if (r0 + n == T && want_logits) lm_head(1, x_ + (size_t)(n - 1) * d, d);
-      if (fold) embed_fold(*fold, x_, n, start_pos + r0, r0 + n == T);
-      if (score) score_fold(*score, x_, n, r0);
-    }
-  } catch (...) {
-    std::swap(x_, pf_x_); std::swap(q_, pf_q_); std::swap(qkv_, pf_qkv_); std::swap(attn_, pf_attn_);
-    std::swap(ff_, pf_ff_); std::swap(opart_, pf_opart_); std::swap(ml_, pf_ml_);
-    d_tokens_ = save_tok; d_pos_ = save_pos; d_seqlen_ = save_sl; d_slot_ = save_slot;
-    throw;
-  }
-  std::swap(x_, pf_x_); std::swap(q_, pf_q_); std::swap(qkv_, pf_qkv_); std::swap(attn_, pf_attn_);
-  std::swap(ff_, pf_ff_); std::swap(opart_, pf_opart_); std::swap(ml_, pf_ml_);
-  d_tokens_ = save_tok; d_pos_ = save_pos; d_seqlen_ = save_sl; d_slot_ = save_slot;
+  if (gemm_prefill_ok(T)) prefill_gemm(slot, tokens, start_pos, want_logits, hook);
+  else prefill_gemv(slot, tokens, start_pos, want_logits, hook);
   std::vector<float> out;
   if (want_logits) {
-    out.resize(V);
-    HIP_CHECK(hipMemcpyAsync(out.data(), logits_, (size_t)V * 4, hipMemcpyDeviceToHost, stream_));
+    out.resize(cfg_.vocab_size);
+    HIP_CHECK(hipMemcpyAsync(out.data(), logits_, (size_t)cfg_.vocab_size * 4, hipMemcpyDeviceToHost, stream_));
   }
   HIP_CHECK(hipStreamSynchronize(stream_));
   return out;
@@ -1674,7 +1535,10 @@ std::vector<float> Engine::embed_prefill(int slot, const std::vector<int>& token
   }
   emb_pos_[slot] = -1;  // (a call that throws leaves no state to continue)
   const EmbedFold fold{slot, pooling, final};
-  prefill_run(slot, tokens, start_pos, false, &fold);
+  ChunkHook hook;
+  hook.fn = [&](const float* x, int n, int row0, bool last) { embed_fold(fold, x, n, start_pos + row0, last); };
+  hook.deterministic = true;  // the same tokens pool to the same bytes (engine.h)
+  prefill_run(slot, tokens, start_pos, false, hook);
   emb_pos_[slot] = start_pos + T;
   emb_mode_[slot] = pooling;
   if (!final) return {};
@@ -1726,10 +1590,7 @@ void Engine::score_lm_head(int n, const float* x, int ldx) {
   const int d = cfg_.d_model, V = cfg_.vocab_size;
   if (gm_ok_ && n >= 5 && n <= gm_rows_ && V % 64 == 0 && gemm_supports(output_.w.qtype)) {
     launch_rmsnorm_bf16(x, ldx, out_norm_, gm_a16_, d, n, d, cfg_.norm_eps, stream_);
-    GemmQArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.A = gm_a16_; g.lda = d; g.M = n; g.K = d; g.nseg = 1; g.seg[0] = output_.w; g.N = V;
-    g.C = sc_logits_; g.ldc = V; g.epi = GEPI_STORE;
+    GemmQArgs g = gemm_args(gm_a16_, d, n, d, output_.w, V, V, sc_logits_, GEPI_STORE);
     gemm(g);
     return;
   }
@@ -1794,7 +1655,9 @@ Engine::PromptScores Engine::score_prefill(int slot, const std::vector<int>& tok
     sc_topn_val_ = top_n;
   }
   const ScoreFold sf{top_n, T};
-  prefill_run(slot, tokens, start_pos, want_logits, nullptr, &sf);
+  ChunkHook hook;
+  hook.fn = [&](const float* x, int n, int row0, bool) { score_fold(sf, x, n, row0); };
+  prefill_run(slot, tokens, start_pos, want_logits, hook);
   // one copy of what the call staged: [T][2] floats | [T][2] ints (| [T][LOGPROB_ROW] floats | ... ints)
   const size_t nbytes = (size_t)T * (16 + (top_n > 0 ? (size_t)LOGPROB_ROW * 8 : 0));
   std::vector<char> host(nbytes);
@@ -1834,37 +1697,21 @@ std::vector<int> Engine::decode(const std::vector<int>& slots, const std::vector
   if (!seeds.empty() && (int)seeds.size() != B) throw std::runtime_error("decode: seeds size mismatch");
   if (B < 1 || B > cfg_.max_batch) throw std::runtime_error("decode: batch out of range");
   if ((int)tokens.size() != B || (int)pos.size() != B) throw std::runtime_error("decode: size mismatch");
-  if (proc_rows_ && proc_rows_ != B) {  // (before the step changes any state)
-    proc_rows_ = 0;
-    throw std::runtime_error("decode: sample processors staged for another batch size");
-  }
-  std::vector<int> sl(B);
+  const ProcessorStage proc_stage(proc_rows_, B, "decode");  // (before the step changes any state)
   for (int b = 0; b < B; ++b) {
     if (pos[b] < 0 || pos[b] >= cfg_.max_ctx) throw std::runtime_error("decode: position out of range");
     if (slots[b] < 0 || slots[b] >= cfg_.max_slots) throw std::runtime_error("decode: bad slot");
     if (tokens[b] < 0 || tokens[b] >= cfg_.vocab_size) throw std::runtime_error("decode: token out of range");
-    sl[b] = pos[b] + 1;
   }
   row_slots_ = slots;
   row_pos_ = pos;
-  const int Bm = cfg_.max_batch;
   const size_t mbytes = (size_t)B * ((cfg_.vocab_size + 7) / 8);
   sample_mask_ = !mask.empty();
   if (sample_mask_ && mask.size() != mbytes) throw std::runtime_error("decode: mask size mismatch");
-  // one pinned staging block -> one async copy (layout: see finalize)
-  *(uint64_t*)h_par_ = seed;  // device-resident seed: one captured graph per (B, masked) serves every request
-  int* hs = (int*)(h_par_ + 8);
-  int *ht = hs + Bm, *hp = ht + Bm, *hl = hp + Bm, *hk = hl + Bm;
-  float* hT = (float*)(hk + Bm);
-  float* hP = hT + Bm;
-  for (int b = 0; b < B; ++b) {
-    hs[b] = slots[b]; ht[b] = tokens[b]; hp[b] = pos[b]; hl[b] = sl[b];
-    hk[b] = b < (int)top_k.size() ? top_k[b] : 0;
-    hT[b] = b < (int)temperature.size() ? temperature[b] : 0.f;
-    hP[b] = b < (int)top_p.size() ? top_p[b] : 1.f;
-  }
-  fill_row_seeds((uint64_t*)(h_par_ + ((char*)d_seeds_ - d_par_)), B, seed, seeds);
-  size_t nbytes = (size_t)((char*)d_seeds_ - d_par_) + (size_t)Bm * 8;
+  // one pinned staging block -> one async copy; the device-resident seed lets one captured graph per
+  // (B, masked) serve every request
+  write_step_params(h_par_, slots, tokens, pos, temperature, top_k, top_p, seed, seeds);
+  size_t nbytes = par_seeds_off_ + (size_t)cfg_.max_batch * 8;
   if (sample_mask_) {
     std::memcpy(h_par_ + par_mask_off_, mask.data(), mbytes);
     nbytes = par_mask_off_ + mbytes;
@@ -1920,13 +1767,8 @@ std::vector<int> Engine::resample(int B, const std::vector<float>& temperature, 
     if (mask.size() != mbytes) throw std::runtime_error("resample: mask size mismatch");
     HIP_CHECK(hipMemcpyAsync(d_mask_, mask.data(), mbytes, hipMemcpyHostToDevice, stream_));
   }
-  SampleArgs s;
-  std::memset(&s, 0, sizeof(s));
-  s.logits = logits_; s.ldl = cfg_.vocab_size; s.B = B; s.V = cfg_.vocab_size;
-  s.temperature = d_temp_; s.top_k = d_topk_; s.seed_dev = d_seed_; s.seeds = d_seeds_;
-  s.tokens = d_tokens_; s.pos = d_pos_; s.advance = 0;
-  s.mask = mask.empty() ? nullptr : d_mask_;
-  s.top_p = d_topp_; s.ws = sample_ws_; s.ws_bytes = sample_ws_bytes_; s.counters = sample_cnt_;
+  SampleArgs s = sample_args(B, !mask.empty());
+  s.seed_dev = d_seed_; s.pos = d_pos_; s.advance = 0;
   take_processors(s, B);
   // pos was advanced by the step: RNG key uses pos[b] (a different stream than the first sample)
   launch_sample(s, stream_);
@@ -1958,13 +1800,8 @@ int Engine::sample_first(int pos, float temperature, int top_k, float top_p, uin
   HIP_CHECK(hipMemcpyAsync(d_seeds_, &seed, 8, hipMemcpyHostToDevice, stream_));
   HIP_CHECK(hipMemcpyAsync(d_fpos_, &pos, 4, hipMemcpyHostToDevice, stream_));
   if (!mask.empty()) HIP_CHECK(hipMemcpyAsync(d_mask_, mask.data(), mbytes, hipMemcpyHostToDevice, stream_));
-  SampleArgs s;
-  std::memset(&s, 0, sizeof(s));
-  s.logits = logits_; s.ldl = cfg_.vocab_size; s.B = 1; s.V = cfg_.vocab_size;
-  s.temperature = d_temp_; s.top_k = d_topk_; s.seeds = d_seeds_;
-  s.tokens = d_tokens_; s.pos = d_fpos_; s.advance = 0;
-  s.mask = mask.empty() ? nullptr : d_mask_;
-  s.top_p = d_topp_; s.ws = sample_ws_; s.ws_bytes = sample_ws_bytes_; s.counters = sample_cnt_;
+  SampleArgs s = sample_args(1, !mask.empty());
+  s.pos = d_fpos_; s.advance = 0;  // (no seed_dev: the key is the row seed and pos alone)
   take_processors(s, 1);
   launch_sample(s, stream_);
   take_logprobs(1);
@@ -2031,16 +1868,13 @@ void Engine::decode_loop_run(int B, int n_steps, bool use_graph) {
   for (int i = 0; i < n_steps; ++i) HIP_CHECK(hipGraphLaunch(ge, stream_));
 }
 
-// the captured decode step for (B, sample_mask_): captured once, replayed for every request --
-// the kernels read tokens / positions / slots / sampling parameters from device arrays
-hipGraphExec_t Engine::step_graph(int B) {
-  const int key = B * 4 + (sample_mask_ ? 1 : 0);
+hipGraphExec_t Engine::graph_for(int key, const std::function<void()>& enqueue) {
   auto it = graphs_.find(key);
   if (it == graphs_.end()) {
     hipGraph_t g;
     HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
     try {
-      enqueue_decode_step(B);
+      enqueue();
     } catch (...) {
       hipStreamEndCapture(stream_, &g);
       throw;
@@ -2054,26 +1888,35 @@ hipGraphExec_t Engine::step_graph(int B) {
   return it->second;
 }
 
+// the captured decode step for (B, sample_mask_): captured once, replayed for every request --
+// the kernels read tokens / positions / slots / sampling parameters from device arrays
+hipGraphExec_t Engine::step_graph(int B) {
+  return graph_for(B * 4 + (sample_mask_ ? 1 : 0), [&] { enqueue_decode_step(B); });
+}
+
 // the forward of a decode step without its sampler (the pipelined decode's graph)
 hipGraphExec_t Engine::forward_graph(int B) {
-  const int key = B * 4 + 2;
-  auto it = graphs_.find(key);
-  if (it == graphs_.end()) {
-    hipGraph_t g;
-    HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-    try {
-      enqueue_decode_forward(B);
-    } catch (...) {
-      hipStreamEndCapture(stream_, &g);
-      throw;
-    }
-    HIP_CHECK(hipStreamEndCapture(stream_, &g));
-    hipGraphExec_t ge;
-    HIP_CHECK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    HIP_CHECK(hipGraphDestroy(g));
-    it = graphs_.emplace(key, ge).first;
+  return graph_for(B * 4 + 2, [&] { enqueue_decode_forward(B); });
+}
+
+void Engine::write_step_params(char* hpar, const std::vector<int>& slots, const std::vector<int>& tokens,
+                               const std::vector<int>& pos, const std::vector<float>& temperature,
+                               const std::vector<int>& top_k, const std::vector<float>& top_p, uint64_t seed,
+                               const std::vector<uint64_t>& seeds) {
+  const int B = (int)slots.size();
+  *(uint64_t*)hpar = seed;
+  int *hs = (int*)(hpar + par_off(PAR_SLOT)), *ht = (int*)(hpar + par_off(PAR_TOKEN));
+  int *hp = (int*)(hpar + par_off(PAR_POS)), *hl = (int*)(hpar + par_off(PAR_SEQLEN));
+  int* hk = (int*)(hpar + par_off(PAR_TOPK));
+  float *hT = (float*)(hpar + par_off(PAR_TEMP)), *hP = (float*)(hpar + par_off(PAR_TOPP));
+  for (int b = 0; b < B; ++b) {
+    hs[b] = slots[b]; hp[b] = pos[b]; hl[b] = pos[b] + 1;
+    if (!tokens.empty()) ht[b] = tokens[b];
+    hk[b] = b < (int)top_k.size() ? top_k[b] : 0;
+    hT[b] = b < (int)temperature.size() ? temperature[b] : 0.f;
+    hP[b] = b < (int)top_p.size() ? top_p[b] : 1.f;
   }
-  return it->second;
+  fill_row_seeds((uint64_t*)(hpar + par_seeds_off_), B, seed, seeds);
 }
 
 void Engine::decode_submit(const std::vector<int>& slots, const std::vector<int>& tokens, const std::vector<int>& pos,
@@ -2092,26 +1935,12 @@ void Engine::decode_submit(const std::vector<int>& slots, const std::vector<int>
     if (!tokens.empty() && (tokens[b] < 0 || tokens[b] >= cfg_.vocab_size))
       throw std::runtime_error("decode_submit: token out of range");
   }
-  const int Bm = cfg_.max_batch;
   par_buf_ ^= 1;  // the other half: the previous submit's copy may not have run yet
   char* hpar = h_par_ + (size_t)par_buf_ * par_bytes_;
-  *(uint64_t*)hpar = seed;
-  int* hs = (int*)(hpar + 8);
-  int *ht = hs + Bm, *hp = ht + Bm, *hl = hp + Bm, *hk = hl + Bm;
-  float* hT = (float*)(hk + Bm);
-  float* hP = hT + Bm;
-  for (int b = 0; b < B; ++b) {
-    hs[b] = slots[b]; hp[b] = pos[b]; hl[b] = pos[b] + 1;
-    if (!tokens.empty()) ht[b] = tokens[b];
-    hk[b] = b < (int)top_k.size() ? top_k[b] : 0;
-    hT[b] = b < (int)temperature.size() ? temperature[b] : 0.f;
-    hP[b] = b < (int)top_p.size() ? top_p[b] : 1.f;
-  }
-  const size_t seeds_off = (size_t)((char*)d_seeds_ - d_par_);
-  fill_row_seeds((uint64_t*)(hpar + seeds_off), B, seed, seeds);
-  const size_t tok_off = (size_t)((char*)d_tokens_ - d_par_), end = seeds_off + (size_t)Bm * 8;
+  write_step_params(hpar, slots, tokens, pos, temperature, top_k, top_p, seed, seeds);
+  const size_t tok_off = par_off(PAR_TOKEN), end = par_seeds_off_ + (size_t)cfg_.max_batch * 8;
   if (tokens.empty()) {  // every row array but the tokens the previous sampler left on the device
-    const size_t after = tok_off + (size_t)Bm * 4;
+    const size_t after = par_off(PAR_TOKEN + 1);
     HIP_CHECK(hipMemcpyAsync(d_par_, hpar, tok_off, hipMemcpyHostToDevice, stream_));
     HIP_CHECK(hipMemcpyAsync(d_par_ + after, hpar + after, end - after, hipMemcpyHostToDevice, stream_));
   } else {

@@ -283,6 +283,36 @@ def test_prefill_gemm_vs_gemv_path(model_files, monkeypatch):
     assert np.abs(l1 - l2).max() < 2e-2 * max(np.abs(l1).max(), 1.0)
 
 
+def test_gemv_prefill_chunk_seam_and_decode_independence(model_files, monkeypatch):
+    """The GEMV-path prefill across its 64-row chunk seam (70 tokens: a second chunk whose 6 rows are one
+    ragged sub-batch) against the fp32 reference, run on another slot BETWEEN the decode steps of a
+    sequence: the prefill works on its own buffers, so that sequence's greedy tokens are those of an
+    identical engine that never ran it."""
+    path = model_files["Q4_K_M"]
+    monkeypatch.setenv("AIOS_PREFILL_GEMM", "0")
+    short = [1, 30, 40, 50, 60, 70, 80]
+    long = [1] + list(np.random.default_rng(5).integers(3, 200, 69))
+
+    def run(interleave):
+        eng, _ = _load(path)
+        tok = int(np.argmax(np.asarray(eng.prefill(0, short, 0, True))))
+        pos, got, logits = len(short), [], None
+        for step in range(4):
+            if interleave and step == 2:
+                logits = torch.from_numpy(np.asarray(eng.prefill(1, long, 0, True)))
+            tok = eng.decode([0], [tok], [pos])[0]
+            pos += 1
+            got.append(tok)
+        return got, logits
+
+    got, logits = run(True)
+    alone, _ = run(False)
+    rl = ReferenceModel.from_gguf(path, kv_bf16=True, act_q8=True).forward(long)[-1]
+    err, scale = (logits - rl).abs().max().item(), rl.abs().max().item()
+    assert err < 2e-2 * max(scale, 1.0), (err, scale)
+    assert got == alone
+
+
 @pytest.mark.parametrize("B", [2, 3, 4])
 @pytest.mark.parametrize("graph", [False, True])
 def test_batched_decode_gemm_path_matches_gemv_path(model_files, monkeypatch, B, graph):
