@@ -285,6 +285,21 @@ PYBIND11_MODULE(_engine, m) {
            py::arg("slots"), py::arg("tokens"), py::arg("pos"), py::arg("temperature") = std::vector<float>{},
            py::arg("top_k") = std::vector<int>{}, py::arg("seed") = 0, py::arg("mask") = py::bytes(),
            py::arg("top_p") = std::vector<float>{}, py::arg("seeds") = std::vector<uint64_t>{})
+      .def("spec_decode",
+           [](Engine& e, int slot, const std::vector<int>& tokens, int pos0, float temperature, int top_k, float top_p,
+              uint64_t seed, py::bytes masks) {
+             // (accepted, tokens): the accepted drafts and the accepted + 1 emitted tokens
+             std::string m = masks;  // R rows of ceil(V/8) bytes (or empty)
+             std::vector<uint8_t> mv(m.begin(), m.end());
+             Engine::SpecResult r;
+             {
+               py::gil_scoped_release nogil;
+               r = e.spec_decode(slot, tokens, pos0, temperature, top_k, top_p, seed, mv);
+             }
+             return py::make_tuple(r.accepted, r.tokens);
+           },
+           py::arg("slot"), py::arg("tokens"), py::arg("pos0"), py::arg("temperature") = 0.f, py::arg("top_k") = 0,
+           py::arg("top_p") = 1.f, py::arg("seed") = 0, py::arg("masks") = py::bytes())
       .def("decode_submit",
            [](Engine& e, const std::vector<int>& slots, const std::vector<int>& tokens, const std::vector<int>& pos,
               const std::vector<float>& temperature, const std::vector<int>& top_k, uint64_t seed,
@@ -812,6 +827,22 @@ PYBIND11_MODULE(_engine, m) {
         },
         py::arg("logits"), py::arg("ldl"), py::arg("R"), py::arg("V"), py::arg("targets"), py::arg("out_f"),
         py::arg("out_i"), py::arg("st"), py::arg("max_grid") = 0);
+  m.attr("SPEC_MAX_ROWS") = SPEC_MAX_ROWS;
+  m.attr("SPEC_RECORD") = SPEC_RECORD;
+  m.def("spec_accept",
+        [](uintptr_t in, uintptr_t out, int pos0, int R, uintptr_t record, uintptr_t tokens, uintptr_t pos,
+           uintptr_t seq_len, uintptr_t history, int hist_stride, uintptr_t st) {
+          // in / out: [R] ints; record: [SPEC_RECORD]; tokens / pos / seq_len: the step state (row 0 written);
+          // history: row 0's [hist_stride] or 0
+          SpecAcceptArgs a;
+          std::memset(&a, 0, sizeof(a));
+          a.in = (const int*)in; a.out = (const int*)out; a.pos0 = pos0; a.R = R; a.record = (int*)record;
+          a.tokens = (int*)tokens; a.pos = (int*)pos; a.seq_len = (int*)seq_len;
+          a.history = (int*)history; a.hist_stride = hist_stride;
+          launch_spec_accept(a, S(st));
+        },
+        py::arg("in_tokens"), py::arg("out_tokens"), py::arg("pos0"), py::arg("R"), py::arg("record"), py::arg("tokens"),
+        py::arg("pos"), py::arg("seq_len"), py::arg("history"), py::arg("hist_stride"), py::arg("st"));
   m.attr("EMBED_NONE") = (int)EMBED_NONE;
   m.attr("EMBED_MEAN") = (int)EMBED_MEAN;
   m.attr("EMBED_LAST") = (int)EMBED_LAST;

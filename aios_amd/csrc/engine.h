@@ -167,6 +167,28 @@ class Engine {
   // logits of the last decode (B x V) -- host copy
   std::vector<float> last_logits(int B);
 
+  // Speculative decoding (ops.h SpecAcceptArgs: the rule): one request's R consecutive positions as the R
+  // rows of one decode step.  tokens[0] is the request's last accepted token (at pos0), tokens[1..R) a draft
+  // of what follows; rows are (slot, tokens[i], pos0 + i), every row samples with the request's parameters
+  // and seeds[i] = seed, so row i draws what a one-row step at pos0 + i would.  Runs the B = R forward graph
+  // (the same graph key as decode's), the eager sampler with the rows' masks (R rows or empty), the staged
+  // processors / logprobs with decode()'s contract (staged for R rows, one shot; last_logprobs() reports R
+  // rows, the caller uses the first accepted + 1), then the accept kernel, and returns after one copy of its
+  // record.  Afterwards: the slot holds valid K/V for [0, pos0 + accepted + 1) -- the positions behind hold
+  // the rejected rows' K/V, which nothing reads and the next write there replaces (the pipelined scheduler's
+  // rule for its dropped forward), and their blocks stay mapped to the slot; the step state is one row at
+  // pos0 + accepted + 1 whose token is on the device, so a B = 1 decode_submit(tokens = {}) continues from
+  // it; logits_ keeps the R rows (last_logits(R)).  Throws before any state changes on: R outside
+  // 2..min(max_batch, SPEC_MAX_ROWS), pos0 + R > max_ctx, a token out of range, a mask that is not R rows, a
+  // tensor-parallel engine, a pipelined step in flight (sampled by decode_sample and not yet collected; a
+  // forward that was submitted and never sampled -- the scheduler's dropped forward -- does not count).
+  struct SpecResult {
+    int accepted = 0;
+    std::vector<int> tokens;  // accepted + 1 of them
+  };
+  SpecResult spec_decode(int slot, const std::vector<int>& tokens, int pos0, float temperature, int top_k, float top_p,
+                         uint64_t seed, const std::vector<uint8_t>& masks);
+
   // Pipelined decode (the serving scheduler's fast path): decode() split so that the forward of step
   // t+1 is enqueued before the host has seen step t's token -- the rows' tokens are the ones step t's
   // sampler left on the device -- and only the sampler waits for the host's grammar mask:
@@ -338,7 +360,8 @@ class Engine {
     a.kv_scale_k = kv_scale_[2 * l];
     a.kv_scale_v = kv_scale_[2 * l + 1];
   }
-  int pipe_B_ = 0;                       // rows of the submitted, not yet sampled step
+  int pipe_B_ = 0;                       // rows of the last submitted step (decode_sample's rows; never reset)
+  bool pipe_sampled_ = false;            // decode_sample ran and decode_collect has not: a step is in flight
   int par_buf_ = 0;                      // which half of the double-buffered pinned parameter block
   uint8_t* h_mask_ = nullptr;            // pinned staging of the pipelined sampler's masks
   hipEvent_t pipe_ev_ = nullptr;         // the pipelined sampler's token copy
@@ -482,6 +505,8 @@ class Engine {
   char* d_par_ = nullptr;          // per-step parameter block (seed, slot, token, pos, seq_len, top_k, T, top_p | masks)
   char* h_par_ = nullptr;          // pinned mirror
   int* h_tok_out_ = nullptr;       // pinned sampled tokens
+  int* d_spec_ = nullptr;          // spec_decode: [SPEC_MAX_ROWS] input tokens | [SPEC_RECORD] the accept record
+  int* h_spec_ = nullptr;          // its pinned mirror
   size_t par_bytes_ = 0, par_mask_off_ = 0;
   void* sample_ws_ = nullptr;
   size_t sample_ws_bytes_ = 0;

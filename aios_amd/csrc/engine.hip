@@ -106,6 +106,7 @@ Engine::~Engine() {
   if (h_mask_) hipHostFree(h_mask_);
   if (h_proc_) hipHostFree(h_proc_);
   if (h_lp_) hipHostFree(h_lp_);
+  if (h_spec_) hipHostFree(h_spec_);
   if (pipe_ev_) hipEventDestroy(pipe_ev_);
   if (stream_) hipStreamDestroy(stream_);
 }
@@ -602,6 +603,8 @@ void Engine::finalize() {
     HIP_CHECK(hipHostMalloc((void**)&h_lp_, (size_t)Bm * 4 + ob, hipHostMallocDefault));
   }
   d_history_ = ibuf((size_t)Bm * (cfg_.max_ctx + 1));
+  d_spec_ = ibuf(SPEC_MAX_ROWS + SPEC_RECORD);
+  HIP_CHECK(hipHostMalloc((void**)&h_spec_, (size_t)(SPEC_MAX_ROWS + SPEC_RECORD) * 4, hipHostMallocDefault));
   const int R = prefill_rows_;
   pf_x_ = fbuf((size_t)R * d);
   pf_q_ = fbuf((size_t)R * qd);
@@ -1742,6 +1745,71 @@ std::vector<int> Engine::decode(const std::vector<int>& slots, const std::vector
   return std::vector<int>(h_tok_out_, h_tok_out_ + B);
 }
 
+Engine::SpecResult Engine::spec_decode(int slot, const std::vector<int>& tokens, int pos0, float temperature, int top_k,
+                                       float top_p, uint64_t seed, const std::vector<uint8_t>& masks) {
+  const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  const int R = (int)tokens.size();
+  const LogprobStage lp_stage(lp_rows_, R, "spec_decode");  // (before the step changes any state)
+  if (cfg_.tp_size > 1) throw std::runtime_error("spec_decode: not available on a tensor-parallel engine");
+  if (pipe_sampled_) throw std::runtime_error("spec_decode: a pipelined step is in flight");
+  if (R < 2 || R > std::min(cfg_.max_batch, SPEC_MAX_ROWS)) throw std::runtime_error("spec_decode: rows out of range");
+  if (slot < 0 || slot >= cfg_.max_slots) throw std::runtime_error("spec_decode: bad slot");
+  if (pos0 < 0 || pos0 + R > cfg_.max_ctx) throw std::runtime_error("spec_decode: positions out of range");
+  const ProcessorStage proc_stage(proc_rows_, R, "spec_decode");  // (before the step changes any state)
+  for (int t : tokens)
+    if (t < 0 || t >= cfg_.vocab_size) throw std::runtime_error("spec_decode: token out of range");
+  const size_t mbytes = (size_t)R * ((cfg_.vocab_size + 7) / 8);
+  if (!masks.empty() && masks.size() != mbytes) throw std::runtime_error("spec_decode: mask size mismatch");
+  sample_mask_ = !masks.empty();
+  // the rows of decode(): one slot, consecutive positions, the request's parameters and seed on every row
+  row_slots_.assign(R, slot);
+  row_pos_.resize(R);
+  for (int i = 0; i < R; ++i) row_pos_[i] = pos0 + i;
+  par_buf_ ^= 1;  // (decode_submit's rule: the copy of a forward the scheduler queued and dropped may not have run yet)
+  char* hpar = h_par_ + (size_t)par_buf_ * par_bytes_;
+  write_step_params(hpar, row_slots_, tokens, row_pos_, std::vector<float>(R, temperature), std::vector<int>(R, top_k),
+                    std::vector<float>(R, top_p), seed, std::vector<uint64_t>(R, seed));
+  size_t nbytes = par_seeds_off_ + (size_t)cfg_.max_batch * 8;
+  if (sample_mask_) {
+    std::memcpy(hpar + par_mask_off_, masks.data(), mbytes);
+    nbytes = par_mask_off_ + mbytes;
+  }
+  HIP_CHECK(hipMemcpyAsync(d_par_, hpar, nbytes, hipMemcpyHostToDevice, stream_));
+  // the input tokens once more, apart from d_tokens_ (the sampler overwrites those)
+  std::copy(tokens.begin(), tokens.end(), h_spec_);
+  HIP_CHECK(hipMemcpyAsync(d_spec_, h_spec_, (size_t)R * 4, hipMemcpyHostToDevice, stream_));
+  for (int i = 0; i < R; ++i) kv_prepare_write(slot, pos0 + i, pos0 + i + 1);
+  kv_sync(R);
+  HIP_CHECK(hipGraphLaunch(forward_graph(R), stream_));
+  int* h_rec = h_spec_ + SPEC_MAX_ROWS;
+  try {
+    enqueue_sample(R, true);
+    take_logprobs(R);
+    SpecAcceptArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = d_spec_; a.out = d_tokens_; a.pos0 = pos0; a.R = R;
+    a.record = d_spec_ + SPEC_MAX_ROWS;
+    a.tokens = d_tokens_; a.pos = d_pos_; a.seq_len = d_seqlen_;
+    a.history = d_history_; a.hist_stride = cfg_.max_ctx + 1;
+    launch_spec_accept(a, stream_);
+  } catch (...) {
+    sample_mask_ = false;
+    throw;
+  }
+  sample_mask_ = false;
+  HIP_CHECK(hipMemcpyAsync(h_rec, d_spec_ + SPEC_MAX_ROWS, (size_t)SPEC_RECORD * 4, hipMemcpyDeviceToHost, stream_));
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  SpecResult r;
+  r.accepted = std::min(std::max(h_rec[0], 0), R - 1);
+  r.tokens.assign(h_rec + 1, h_rec + 2 + r.accepted);
+  // the step state is one row now: the sequence at pos0 + accepted + 1
+  row_slots_.assign(1, slot);
+  row_pos_.assign(1, pos0 + r.accepted + 1);
+  return r;
+}
+
 std::vector<int> Engine::resample(int B, const std::vector<float>& temperature, const std::vector<int>& top_k,
                                   uint64_t seed, const std::vector<uint8_t>& mask, const std::vector<float>& top_p) {
   const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
@@ -1982,12 +2050,14 @@ void Engine::decode_sample(const std::vector<uint8_t>& mask) {
   sample_mask_ = false;
   HIP_CHECK(hipMemcpyAsync(h_tok_out_, d_tokens_, B * 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipEventRecord(pipe_ev_, stream_));
+  pipe_sampled_ = true;
 }
 
 std::vector<int> Engine::decode_collect() {
   const int B = pipe_B_;
   if (B < 1) throw std::runtime_error("decode_collect: no sampled step");
   HIP_CHECK(hipEventSynchronize(pipe_ev_));
+  pipe_sampled_ = false;
   return std::vector<int>(h_tok_out_, h_tok_out_ + B);
 }
 

@@ -256,6 +256,35 @@ struct ScoreArgs {
 };
 void launch_score_rows(const ScoreArgs& a, hipStream_t st);
 
+// ---- speculative decoding: accept a draft ---------------------------------------------------------
+// One request ran R consecutive positions pos0 .. pos0 + R - 1 as the R rows of one decode step: in[0] is its
+// last accepted token, in[1..R) a draft of the tokens that follow, and the R-row sampler launch in front (on
+// the same stream, advance = 1) wrote out[i], the token after in[0..i].  Row i saw the right context only if
+// the drafts before it were right, so
+//   n = the largest k <= R - 1 with out[i] == in[i + 1] for every i < k  (a match behind the first mismatch
+//   does not count), and the request emits out[0..n]: what n + 1 one-row steps would have sampled, because
+//   the sampler's RNG is keyed (seeds[b], pos[b]) and not by step.
+// Writes: record[SPEC_RECORD] = {n, out[0..n], -1 ...} for one copy to the host, and row 0 of the step state
+// as if the sequence had advanced by n + 1 one-row steps: tokens[0] = out[n], pos[0] = pos0 + n + 1,
+// seq_len[0] = pos0 + n + 2, history[pos0 + 1 + i] = out[i] for i <= n (row 0's history; entries at or past
+// hist_stride are not written).  Rows 1..R-1 of the state are left as the sampler wrote them: the next step's
+// upload overwrites them.  out may be tokens (every out[i] is read before tokens[0] is written).  One
+// workgroup of one wave, no workspace, no atomics.  kernels/spec_accept.hip; tests/spec_oracle.py is the rule.
+constexpr int SPEC_MAX_ROWS = 8;                  // rows of a speculative step: the last token + 7 drafts
+constexpr int SPEC_RECORD = SPEC_MAX_ROWS + 1;    // ints of the packed record
+struct SpecAcceptArgs {
+  const int* in;    // [R] the step's input tokens (a copy of its own: the sampler overwrites tokens[])
+  const int* out;   // [R] what the sampler wrote
+  int pos0, R;      // R in 2..SPEC_MAX_ROWS
+  int* record;      // [SPEC_RECORD]
+  int* tokens;      // step state, row 0 written
+  int* pos;
+  int* seq_len;
+  int* history;     // row 0's history or null
+  int hist_stride;
+};
+void launch_spec_accept(const SpecAcceptArgs& a, hipStream_t st);
+
 // ---- text embeddings ---------------------------------------------------------------------------
 // Pooled embedding of hidden rows x[t] (the residual stream before output_norm), llama.cpp's --embedding
 // rule for a causal model:  h[t] = x[t] * g * rsqrt(mean(x[t]^2) + eps)  (the model's final RMSNorm);

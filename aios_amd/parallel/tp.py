@@ -350,6 +350,11 @@ class TPEngine:
             # engines only"; the hidden state is replicated, so this is scope, not design): hidden like the
             # logprob calls, so the scheduler fails that request alone and /v1/embeddings answers 400
             raise AttributeError(name)
+        if name == "spec_decode":
+            # no speculative decoding on a tensor-parallel tier (the shard's Engine.spec_decode throws: its
+            # accept step is not broadcast to the workers): hidden, so the scheduler sees a tier that cannot
+            # speculate, decodes plainly, logs that once and reports 0 / 0 drafted
+            raise AttributeError(name)
         attr = getattr(self._eng, name)
         if name not in self._FORWARD or not callable(attr):
             return attr
@@ -476,6 +481,41 @@ def spec_sampling(path: str) -> dict:
         k, _, v = kv.partition("=")
         if k in _SAMPLING_KEYS:
             out[_SAMPLING_KEYS[k]] = float(v)
+    return out
+
+
+_SPEC_KEYS = {"spec": "mode", "specdraft": "draft_max", "specnmin": "ngram_min", "specnmax": "ngram_max",
+              "specctx": "max_context"}
+
+
+def spec_speculative(path: str) -> dict:
+    """the '#...&spec=lookup&specdraft=7&specnmin=2&specnmax=3&specctx=4096' fragments of a model spec: the
+    tier's speculative-decoding settings (Scheduler's `speculative`); only the ones present"""
+    out = {}
+    for kv in filter(None, path.partition("#")[2].split("&")):
+        k, _, v = kv.partition("=")
+        if k not in _SPEC_KEYS:
+            continue
+        if k == "spec":
+            if v in ("off", "lookup"):
+                out["mode"] = v
+            else:
+                log.warning("model spec: spec=%r is neither 'off' nor 'lookup'; the default is kept", v)
+            continue
+        try:
+            out[_SPEC_KEYS[k]] = int(v)
+        except ValueError:
+            log.warning("model spec: %s=%r is not an integer; the default is kept", k, v)
+    # out-of-range values: the default is kept and said, as the node config does for the tier's fields
+    lo, hi = out.get("ngram_min", 2), out.get("ngram_max", 3)
+    if not 1 <= lo <= hi <= 8:
+        log.warning("model spec: specnmin / specnmax need 1 <= min <= max <= 8; the defaults are kept")
+        out.pop("ngram_min", None)
+        out.pop("ngram_max", None)
+    for key, ok in (("draft_max", lambda x: 1 <= x <= 7), ("max_context", lambda x: x >= 1)):
+        if key in out and not ok(out[key]):
+            log.warning("model spec: %s=%d is out of range; the default is kept", key, out[key])
+            del out[key]
     return out
 
 

@@ -187,7 +187,8 @@ class ModelManager:
         from .tokenizer import SpmTokenizer, from_gguf
 
         E = native.require()
-        from ..parallel.tp import launch_tp, parse_spec, spec_kv_calibrate, spec_kv_dtype, spec_sampling
+        from ..parallel.tp import (launch_tp, parse_spec, spec_kv_calibrate, spec_kv_dtype, spec_sampling,
+                                   spec_speculative)
 
         device = self.device if m.device < 0 else m.device
 
@@ -255,7 +256,8 @@ class ModelManager:
         slots = getattr(eng.config, "max_slots", self.max_slots)
         batch = getattr(eng.config, "max_batch", self.max_batch)
         m.scheduler = Scheduler(eng, tok, min(batch, self.max_batch), min(slots, self.max_slots), m.context_length,
-                                m.grammar, name=m.name, sampling_defaults=spec_sampling(m.path))
+                                m.grammar, name=m.name, sampling_defaults=spec_sampling(m.path),
+                                speculative=spec_speculative(m.path))
         # capture every batch size's decode-step graph now, not on the first step that reaches it
         # (a capture stalls that step by milliseconds; AIOS_GRAPH_WARMUP=0 skips)
         capture = getattr(eng, "capture_graphs", None)

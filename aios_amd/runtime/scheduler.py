@@ -37,6 +37,7 @@ import numpy as np
 
 from . import embedding as host_embedding
 from . import sampler as host_sampler
+from . import speculative as speculative_mod
 
 log = logging.getLogger("aios.runtime.scheduler")
 
@@ -83,6 +84,12 @@ class GenRequest:
     # prefilled from position 0 (cached positions have no logits) and generation proceeds as usual; with
     # such a request max_tokens may be 0: it then finishes "length" with no sampled token
     prompt_logprobs: Optional[int] = None
+    # speculative decoding from prompt-lookup drafts (runtime/speculative.py: the rule): None = the tier's
+    # default, True / False = on / off for this request.  The tokens are the ones plain decode would emit;
+    # only the number of engine steps changes.  prediction_ids: the tokens of a text the caller expects in
+    # the output (OpenAI's Predicted Outputs), searched for drafts before the prompt itself
+    speculative: Optional[bool] = None
+    prediction_ids: Optional[List[int]] = None
     stop_ids: Optional[List[int]] = None
     on_delta: Optional[Callable[[str], None]] = None
     on_done: Optional[Callable[["GenResult"], None]] = None
@@ -111,11 +118,21 @@ class GenResult:
     # logprob), ...]) per prompt token; rank 0 = the token was the model's argmax, the alternatives are the
     # best tokens AT that position, best first; the first token has no distribution: None, None, []
     prompt_logprobs: Optional[list] = None
+    # speculative decoding: draft tokens handed to the engine for verification, and how many of them it
+    # accepted (both 0 when nothing was drafted)
+    draft_tokens: int = 0
+    accepted_draft_tokens: int = 0
+
+
+# the tier's speculative-decoding settings (node config: speculative, spec_draft_max, spec_ngram_min / _max,
+# spec_max_context); draft_max and max_context are measured values (profiles/spec_decode.txt)
+SPEC_DEFAULTS = dict(mode="off", draft_max=7, ngram_min=2, ngram_max=3, max_context=4096)
 
 
 class _Seq:
     __slots__ = ("req", "slot", "pos", "last", "out", "grammar_state", "emitted", "t_first", "cached", "todo",
-                 "p_off", "r_off", "seed", "proc", "pen_n", "lp_n", "lps", "embedding", "plp_n", "plps")
+                 "p_off", "r_off", "seed", "proc", "pen_n", "lp_n", "lps", "embedding", "plp_n", "plps",
+                 "spec", "drafter", "drafted", "draft_hits")
 
     def __init__(self, req, slot):
         self.req, self.slot = req, slot
@@ -137,14 +154,33 @@ class _Seq:
         self.embedding = None        # an embedding request's result
         self.plp_n = -1              # prompt logprobs: alternatives per prompt token; -1: not asked
         self.plps: List[tuple] = []  # one entry per prompt token prefilled so far
-        self.p_off = 0               # incremental detokenization window [p_off, r_off) already emitted
+        self.spec = False            # speculative decoding on for this request (set at admission)
+        self.drafter = None          # its LookupDrafter over prompt + out, built when decoding starts
+        self.drafted = 0             # draft tokens verified / accepted so far
+        self.draft_hits = 0
+        self.p_off = 0              # incremental detokenization window [p_off, r_off) already emitted
         self.r_off = 0
 
 
 class Scheduler:
     def __init__(self, engine, tokenizer, max_batch: int, max_slots: int, max_ctx: int, grammar=None,
-                 name: str = "model", sampling_defaults: Optional[Dict[str, float]] = None):
+                 name: str = "model", sampling_defaults: Optional[Dict[str, float]] = None,
+                 speculative: Optional[dict] = None):
         self.engine = engine
+        # speculative decoding (SPEC_DEFAULTS; off unless the tier or a request turns it on); it needs the
+        # engine's spec_decode, which the CPU and tensor-parallel tiers lack: they decode plainly and say so once
+        self.spec = dict(SPEC_DEFAULTS)
+        for k, v in (speculative or {}).items():
+            if k not in SPEC_DEFAULTS:
+                raise ValueError(f"unknown speculative setting {k!r}")
+            self.spec[k] = v if k == "mode" else int(v)
+        if self.spec["mode"] not in ("off", "lookup"):
+            raise ValueError(f"speculative mode {self.spec['mode']!r} is neither 'off' nor 'lookup'")
+        if not (1 <= self.spec["draft_max"] <= speculative_mod.DRAFT_MAX_LIMIT and self.spec["max_context"] >= 1 and
+                1 <= self.spec["ngram_min"] <= self.spec["ngram_max"] <= speculative_mod.NGRAM_MAX_LIMIT):
+            raise ValueError("speculative settings out of range")
+        self.can_spec = hasattr(engine, "spec_decode")
+        self._warned_no_spec = False
         # the tier's logit-processor defaults for requests that leave a field unset (the only way a
         # gRPC caller, whose contract has no such fields, gets them)
         self.sampling_defaults = dict(NEUTRAL_PROCESSORS)
@@ -185,7 +221,7 @@ class Scheduler:
         self.cv = threading.Condition()
         self.stop_flag = False
         self.stats = dict(requests=0, tokens=0, prefill_tokens=0, cached_tokens=0, steps=0, batch_sum=0, errors=0,
-                          embeddings=0, prompt_scores=0)
+                          embeddings=0, prompt_scores=0, spec_steps=0, spec_drafted=0, spec_accepted=0)
         # health / metrics (ModelManager.supervise and HealthCheck details)
         self.max_slots = max_slots
         self.last_progress = time.time()   # last completed admission or decode step
@@ -383,6 +419,12 @@ class Scheduler:
         if proc != tuple(NEUTRAL_PROCESSORS.values()):
             seq.proc = proc
             seq.pen_n = host_sampler.penalty_window(r.repeat_last_n)
+        seq.spec = self.spec["mode"] == "lookup" if r.speculative is None else bool(r.speculative)
+        if seq.spec and not self.can_spec:
+            seq.spec = False
+            if not self._warned_no_spec:
+                self._warned_no_spec = True
+                log.warning("%s: the engine has no spec_decode; speculative decoding is off on this tier", self.name)
         self._begin_prefill(seq, common)
 
     def _prefill_chunk(self, seq: _Seq, whole: bool = False):
@@ -452,6 +494,10 @@ class Scheduler:
                 lp = (x, list(zip(ids, xs)))
         seq.t_first = time.time()
         self.active.append(seq)
+        if seq.spec:  # (before the first token: _accept appends every emitted token to the drafter's context)
+            sp = self.spec
+            seq.drafter = speculative_mod.LookupDrafter(r.prompt_ids, r.prediction_ids, sp["ngram_min"], sp["ngram_max"],
+                                                        sp["draft_max"])
         self._accept(seq, tok, lp)
 
     @staticmethod
@@ -481,6 +527,8 @@ class Scheduler:
                 self._finish(seq, "stop")
                 return False
         seq.out.append(tok)
+        if seq.drafter is not None:
+            seq.drafter.append(tok)
         if seq.lp_n >= 0:
             seq.lps.append((int(tok), lp[0], lp[1]))
         seq.last = tok
@@ -530,7 +578,9 @@ class Scheduler:
                 "prefilling": len(self.prefilling), "queued": len(self.queue),
                 "kv_slot_util": (len(self.active) + len(self.prefilling)) / max(1, self.max_slots),
                 "avg_batch": st["batch_sum"] / st["steps"] if st["steps"] else 0.0,
-                "prefix_hit_tokens": st["cached_tokens"], "errors": st["errors"]}
+                "prefix_hit_tokens": st["cached_tokens"], "errors": st["errors"],
+                # accepted / verified draft tokens of the speculative steps so far (0 when none ran)
+                "spec_accept_rate": st["spec_accepted"] / st["spec_drafted"] if st["spec_drafted"] else 0.0}
 
     def _mask(self, seq: _Seq) -> bytes:
         if len(seq.out) + 1 < seq.req.min_tokens:  # the next token may not complete the object
@@ -596,12 +646,14 @@ class Scheduler:
                                   [s.seed for s in rows])
 
     @staticmethod
-    def _window(s: _Seq) -> List[int]:
-        """the row's penalty window: its last pen_n tokens, prompt tail included"""
+    def _window(s: _Seq, extra=()) -> List[int]:
+        """the row's penalty window: its last pen_n tokens, prompt tail included (extra: draft tokens that
+        stand behind `out` for a row of a speculative step)"""
         n = s.pen_n
         if n <= 0:
             return []
-        return (s.req.prompt_ids[-(n - len(s.out)):] if len(s.out) < n else []) + s.out[-n:]
+        out = s.out + list(extra) if extra else s.out
+        return (s.req.prompt_ids[-(n - len(out)):] if len(out) < n else []) + out[-n:]
 
     def _processors(self, rows):
         """Before a sampler launch: hand the engine the rows' min-p / penalties and penalty windows
@@ -683,7 +735,94 @@ class Scheduler:
         tm["accept_s"] += t2b - t2
         self.step_log.append((t3, len(rows)))
 
+    def _spec_draft(self, s: _Seq):
+        """The draft of s's next speculative step and its rows' masks: the drafter's proposal, trimmed so
+        that no row can run past the request's end -- to max_tokens and the context window, before the first
+        EOS / stop id, and for a grammar row before the first token the grammar rejects or that would
+        complete the value (row i's mask is the grammar's after drafts 0..i-1)."""
+        r = s.req
+        rows_max = min(self.max_batch, speculative_mod.DRAFT_MAX_LIMIT + 1)
+        lim = min(r.max_tokens - len(s.out) - 1, self.max_ctx - s.pos - 2, rows_max - 1)
+        draft = list(s.drafter.draft(lim)) if lim > 0 else []
+        for i, t in enumerate(draft):
+            if t in self.eos or (r.stop_ids and t in r.stop_ids):
+                draft = draft[:i]
+                break
+        masks = b""
+        if draft and s.grammar_state is not None:
+            st = s.grammar_state.copy()
+            ms = [self._mask(s)]
+            for i, t in enumerate(draft):
+                if not self.grammar.accept_token(st, t) or self.grammar.complete(st):
+                    draft = draft[:i]
+                    break
+                open_ = len(s.out) + i + 2 < r.min_tokens  # (_mask's rule for the row behind draft i)
+                ms.append(self.grammar.mask_open(st) if open_ else self.grammar.mask(st))
+            masks = b"".join(ms[:len(draft) + 1])
+        return draft, masks
+
+    def _spec_step(self) -> bool:
+        """A speculative step instead of a plain one, when exactly one sequence decodes, speculation is on
+        for it, nothing is prefilling and its drafter proposes something: the last token and the draft go
+        through the engine as consecutive rows of one step (Engine.spec_decode), and every token it emits
+        is accepted in order, as if each came from a step of its own.  False: nothing ran, the caller takes
+        a plain step."""
+        if len(self.active) != 1 or self.prefilling or not self.active[0].spec:
+            return False
+        s = self.active[0]
+        if self._pending is not None:
+            # The draft needs the in-flight step's token, and collecting it early gives up that step's
+            # overlap of host and device work.  So only when a draft can follow: the context is short enough
+            # and the text in front of the unknown token has occurred before with two tokens behind it (the
+            # drafter's necessary condition; text that does not repeat stays fully pipelined).
+            if s.pos + 2 > self.spec["max_context"] or not s.drafter.may_draft_after_next():
+                return False
+            self._drain()
+            if self.active != [s]:  # (the collected token finished the request, or the step failed)
+                return False
+        if s.pos + 1 > self.spec["max_context"]:  # every row re-reads the slot's K/V: no gain past this
+            return False
+        t0 = time.perf_counter()
+        draft, masks = self._spec_draft(s)
+        if not draft:
+            return False
+        r, R = s.req, len(draft) + 1
+        if s.proc is not None and hasattr(self.engine, "set_sample_processors"):
+            self.engine.set_sample_processors(*[[v] * R for v in s.proc], [self._window(s, draft[:i]) for i in range(R)])
+        rows = [s] * R
+        self._stage_logprobs(rows)
+        t1 = time.perf_counter()
+        acc, out = self.engine.spec_decode(s.slot, [s.last] + draft, s.pos, float(r.temperature),
+                                           int(r.top_k) if r.temperature > 0 else 0,
+                                           float(r.top_p) if 0.0 < r.top_p < 1.0 else 1.0, s.seed, masks)
+        t2 = time.perf_counter()
+        st = self.stats
+        st["steps"] += 1
+        st["batch_sum"] += 1
+        st["spec_steps"] += 1
+        st["spec_drafted"] += len(draft)
+        st["spec_accepted"] += int(acc)
+        s.drafted += len(draft)
+        s.draft_hits += int(acc)
+        lps = self._read_logprobs(rows)
+        for i, t in enumerate(out):  # stops at the first token that finishes the request: the rest is dropped
+            s.pos += 1
+            self.slot_cache[s.slot].append(s.last)
+            if not self._accept(s, int(t), lps[i]):
+                break
+        t3 = time.perf_counter()
+        tm = self.timing
+        tm["mask_s"] += t1 - t0
+        tm["engine_decode_s"] += t2 - t1
+        tm["accept_s"] += t3 - t2
+        self.step_log.append((t3, 1))
+        return True
+
     def _step(self):
+        if self._spec_step():
+            return
+        if not self.active:  # (_spec_step collected a pipelined step whose token finished the last sequence)
+            return
         if self.pipeline:
             return self._step_pipelined()
         B = len(self.active)
@@ -738,7 +877,8 @@ class Scheduler:
             finish_reason=reason, ttft_ms=(seq.t_first - r.submitted_at) * 1e3 if seq.t_first else 0.0,
             latency_ms=(now - r.submitted_at) * 1e3, cached_prompt_tokens=seq.cached, error=error,
             logprobs=list(seq.lps) if seq.lp_n >= 0 else None, embedding=seq.embedding,
-            prompt_logprobs=list(seq.plps) if seq.plp_n >= 0 else None))
+            prompt_logprobs=list(seq.plps) if seq.plp_n >= 0 else None,
+            draft_tokens=seq.drafted, accepted_draft_tokens=seq.draft_hits))
 
     @staticmethod
     def _done(r: GenRequest, res: GenResult):

@@ -87,6 +87,36 @@ def logprobs_from_body(body: dict, scheduler) -> Optional[int]:
     return int(top or 0)
 
 
+def prediction_from_body(body: dict, tokenizer):
+    """`prediction` (OpenAI's Predicted Outputs) and `speculative` (a boolean, an extension) of a chat or
+    completions body: (GenRequest.speculative, GenRequest.prediction_ids).  A prediction turns prompt-lookup
+    speculation on for the request unless `speculative` says otherwise; its text is only a source of drafts,
+    the output is what the model samples.  ValueError (-> 400) for a malformed field."""
+    spec, pred = body.get("speculative"), body.get("prediction")
+    if spec is not None and not isinstance(spec, bool):
+        raise ValueError("speculative must be a boolean")
+    if pred is None:
+        return spec, None
+    if not isinstance(pred, dict) or pred.get("type") != "content":
+        raise ValueError('prediction must be an object of type "content"')
+    content = pred.get("content")
+    if isinstance(content, list) and content and all(
+            isinstance(p, dict) and p.get("type") == "text" and isinstance(p.get("text"), str) for p in content):
+        content = "".join(p["text"] for p in content)
+    if not isinstance(content, str) or not content:
+        raise ValueError('prediction.content must be a non-empty string or a list of {"type": "text", "text": ...} parts')
+    ids = [int(t) for t in tokenizer.encode(content, add_bos=False, parse_special=False)]
+    return (True if spec is None else spec), ids
+
+
+def prediction_usage(res) -> dict:
+    """usage.completion_tokens_details: the draft tokens the engine verified, accepted and not (0 / 0 when
+    nothing was drafted -- speculation off, a tier whose engine cannot speculate, or no draft found)"""
+    acc = int(getattr(res, "accepted_draft_tokens", 0) or 0)
+    return {"accepted_prediction_tokens": acc,
+            "rejected_prediction_tokens": max(int(getattr(res, "draft_tokens", 0) or 0) - acc, 0)}
+
+
 def logprobs_content(tokenizer, entries) -> list:
     """GenResult.logprobs as OpenAI's choices[0].logprobs.content: per token its piece (`bytes`: the
     piece's raw bytes, `token`: their UTF-8 decoding, U+FFFD where the piece alone is not valid UTF-8),
@@ -199,8 +229,10 @@ def completion_request(body: dict, tokenizer, scheduler) -> dict:
         rln = None if rln is None else int(rln)
     except (TypeError, ValueError) as e:
         raise ValueError(f"bad sampling field: {e}") from None
+    speculative, prediction_ids = prediction_from_body(body, tokenizer)
     return dict(ids=ids, prompt_text=text, max_tokens=int(max_tokens), temperature=max(temperature, 0.0),
-                echo=bool(echo), logprobs=lp, stream=stream, sampling=sampling, repeat_last_n=rln)
+                echo=bool(echo), logprobs=lp, stream=stream, sampling=sampling, repeat_last_n=rln,
+                speculative=speculative, prediction_ids=prediction_ids)
 
 
 def completion_logprobs(tokenizer, entries) -> dict:
@@ -256,6 +288,7 @@ async def complete(m, c: dict, on_delta=None, timeout: float = 120.0) -> GenResu
             req.logprobs, req.top_logprobs = True, int(c["logprobs"])
         if c["echo"]:
             req.prompt_logprobs = int(c["logprobs"])
+    req.speculative, req.prediction_ids = c.get("speculative"), c.get("prediction_ids")
     m.scheduler.submit(req)
     try:
         return await asyncio.wait_for(fut, timeout + 5)
@@ -286,9 +319,11 @@ async def embed(m, inputs: List[List[int]], pooling: str, timeout: float = 120.0
 
 async def generate(m, messages, max_tokens: int, temperature: float, json_mode: bool, on_delta=None,
                    timeout: float = 120.0, seed: int = 0, sampling: Optional[dict] = None,
-                   top_logprobs: Optional[int] = None) -> GenResult:
+                   top_logprobs: Optional[int] = None, speculative: Optional[bool] = None,
+                   prediction_ids: Optional[List[int]] = None) -> GenResult:
     """sampling: further GenRequest fields by name (top_p, top_k, seed, min_p, the penalties);
-    top_logprobs: None, or per-token logprobs with that many alternatives (GenResult.logprobs)"""
+    top_logprobs: None, or per-token logprobs with that many alternatives (GenResult.logprobs);
+    speculative / prediction_ids: GenRequest's (prediction_from_body)"""
     loop = asyncio.get_running_loop()
     fut = loop.create_future()
     prompt = m.template.render(messages, add_generation_prompt=True)
@@ -309,6 +344,7 @@ async def generate(m, messages, max_tokens: int, temperature: float, json_mode: 
         setattr(req, k, v)
     if top_logprobs is not None:
         req.logprobs, req.top_logprobs = True, int(top_logprobs)
+    req.speculative, req.prediction_ids = speculative, prediction_ids
     m.scheduler.submit(req)
     try:
         return await asyncio.wait_for(fut, timeout + 5)
@@ -484,6 +520,7 @@ class AIRuntimeService:
                                      status=400)
         try:
             top_logprobs = logprobs_from_body(body, m.scheduler)
+            speculative, prediction_ids = prediction_from_body(body, m.tokenizer)
         except ValueError as e:
             return web.json_response({"error": {"message": str(e), "type": "invalid_request_error"}}, status=400)
         created = int(time.time())
@@ -493,7 +530,8 @@ class AIRuntimeService:
             await resp.prepare(request)
             q: asyncio.Queue = asyncio.Queue()
             task = asyncio.ensure_future(generate(m, messages, max_tokens, temperature, json_mode, on_delta=q.put_nowait,
-                                                  sampling=sampling))
+                                                  sampling=sampling, speculative=speculative,
+                                                  prediction_ids=prediction_ids))
             task.add_done_callback(lambda _t: q.put_nowait(None))
             while True:
                 d = await q.get()
@@ -509,7 +547,7 @@ class AIRuntimeService:
             await resp.write_eof()
             return resp
         res = await generate(m, messages, max_tokens, temperature, json_mode, sampling=sampling,
-                             top_logprobs=top_logprobs)
+                             top_logprobs=top_logprobs, speculative=speculative, prediction_ids=prediction_ids)
         choice = {"index": 0, "message": {"role": "assistant", "content": res.text},
                   "finish_reason": "length" if res.finish_reason == "length" else "stop"}
         if top_logprobs is not None:  # (bodies of requests that did not ask stay as they were)
@@ -518,7 +556,8 @@ class AIRuntimeService:
             "id": rid, "object": "chat.completion", "created": created, "model": m.name,
             "choices": [choice],
             "usage": {"prompt_tokens": res.prompt_tokens, "completion_tokens": res.completion_tokens,
-                      "total_tokens": res.prompt_tokens + res.completion_tokens},
+                      "total_tokens": res.prompt_tokens + res.completion_tokens,
+                      "completion_tokens_details": prediction_usage(res)},
             "timings": {"ttft_ms": res.ttft_ms, "latency_ms": res.latency_ms,
                         "cached_prompt_tokens": res.cached_prompt_tokens},
         })
@@ -578,10 +617,14 @@ class AIRuntimeService:
             lp = completion_logprobs(m.tokenizer, entries)
         choice = {"text": (c["prompt_text"] if c["echo"] else "") + res.text, "index": 0, "logprobs": lp,
                   "finish_reason": "length" if res.finish_reason == "length" else "stop"}
+        usage = {"prompt_tokens": res.prompt_tokens, "completion_tokens": res.completion_tokens,
+                 "total_tokens": res.prompt_tokens + res.completion_tokens}
+        # (the usage of a body that names neither field on a tier that does not speculate stays as it was)
+        if c["speculative"] is not None or getattr(m.scheduler, "spec", {}).get("mode", "off") != "off":
+            usage["completion_tokens_details"] = prediction_usage(res)
         return web.json_response({
             "id": rid, "object": "text_completion", "created": created, "model": m.name, "choices": [choice],
-            "usage": {"prompt_tokens": res.prompt_tokens, "completion_tokens": res.completion_tokens,
-                      "total_tokens": res.prompt_tokens + res.completion_tokens},
+            "usage": usage,
         })
 
     async def _http_embeddings(self, request):

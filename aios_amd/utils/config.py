@@ -53,6 +53,25 @@ class ModelTier:
     repeat_penalty: float = 1.0
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
+    # speculative decoding from prompt-lookup drafts (runtime/speculative.py): "off" | "lookup"; the longest
+    # draft (1..7), the n-gram lengths searched, and the context (keys) above which no draft is tried --
+    # every row of a speculative step re-reads the slot's K/V (profiles/spec_decode.txt: the measured defaults)
+    speculative: str = "off"
+    spec_draft_max: int = 7
+    spec_ngram_min: int = 2
+    spec_ngram_max: int = 3
+    spec_max_context: int = 4096
+
+    def speculative_frag(self) -> List[str]:
+        """the non-default speculative settings as model-spec fragments (parallel.tp.spec_speculative)"""
+        out = []
+        for key, field, default in (("spec", "speculative", "off"), ("specdraft", "spec_draft_max", 7),
+                                    ("specnmin", "spec_ngram_min", 2), ("specnmax", "spec_ngram_max", 3),
+                                    ("specctx", "spec_max_context", 4096)):
+            v = getattr(self, field)
+            if v != default:
+                out.append(f"{key}={v}")
+        return out
 
     def sampling_frag(self) -> List[str]:
         """the non-neutral processor defaults as model-spec fragments (parallel.tp.spec_sampling)"""
@@ -152,6 +171,7 @@ class NodeConfig:
                 if t.kv_calibrate and t.kv_calibrate != "auto":
                     frag.append(f"kvcal={t.kv_calibrate}")
             frag += t.sampling_frag()
+            frag += t.speculative_frag()
             devs = list(t.devices)
             if not devs and t.replicas > 1:
                 devs = list(self.models.devices[:t.replicas]) or list(range(t.replicas))
@@ -191,6 +211,7 @@ class NodeConfig:
                 if t.kv_calibrate and t.kv_calibrate != "auto":
                     frag.append(f"kvcal={t.kv_calibrate}")
             frag += t.sampling_frag()
+            frag += t.speculative_frag()
             out.append((name, path + ("#" + "&".join(frag) if frag else ""), t.context_length))
         return out
 
@@ -274,6 +295,21 @@ def load(path: Optional[str] = None, env=None) -> NodeConfig:
                 cfg_warn.append(f"models.{name}.kv_calibrate: cannot use {tiers[name].kv_calibrate!r}; default kept")
                 cal = "auto"
             tiers[name].kv_calibrate = cal
+            mode = str(tiers[name].speculative).strip().lower()
+            if mode not in ("off", "lookup"):
+                cfg_warn.append(f"models.{name}.speculative: cannot use {tiers[name].speculative!r}; default kept")
+                mode = "off"
+            tiers[name].speculative = mode
+            if not 1 <= tiers[name].spec_draft_max <= 7:
+                cfg_warn.append(f"models.{name}.spec_draft_max: {tiers[name].spec_draft_max} outside 1..7; default kept")
+                tiers[name].spec_draft_max = 7
+            if not 1 <= tiers[name].spec_ngram_min <= tiers[name].spec_ngram_max <= 8:
+                cfg_warn.append(f"models.{name}.spec_ngram_min / spec_ngram_max: need 1 <= min <= max <= 8; defaults kept")
+                tiers[name].spec_ngram_min, tiers[name].spec_ngram_max = 2, 3
+            if tiers[name].spec_max_context < 1:
+                cfg_warn.append(f"models.{name}.spec_max_context: {tiers[name].spec_max_context} is below 1; default kept "
+                                "(speculative = \"off\" turns the feature off)")
+                tiers[name].spec_max_context = 4096
     models = _coerce(ModelsConfig, {k: v for k, v in models_raw.items() if not isinstance(v, dict)}, cfg_warn, "models")
     if isinstance(models_raw.get("devices"), list):
         models.devices = [int(x) for x in models_raw["devices"]]

@@ -36,6 +36,7 @@ HOT = [
     "aios::logprob_kernel*",
     "aios::embed_pool_kernel<*",
     "aios::get_rows_step_kernel*",
+    "aios::spec_accept_kernel*",
 ]
 
 
