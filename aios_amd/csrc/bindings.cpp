@@ -522,6 +522,33 @@ PYBIND11_MODULE(_engine, m) {
         HIP_CHECK(hipDeviceSynchronize());
       });
 
+  // the load-time expansion of the formats no kernel streams (Engine::upload_qmat): n elements of raw
+  // GGUF blocks staged on the device -> bf16 at out
+  m.def("legacy_to_bf16",
+        [](int qt, py::buffer raw, size_t n, uintptr_t out, uintptr_t st) {
+          size_t be = 0, bb = 0;  // block elements / bytes
+          switch (qt) {
+            case QT_F32: be = 1; bb = 4; break;
+            case QT_Q4_1: be = 32; bb = 20; break;
+            case QT_Q5_0: be = 32; bb = 22; break;
+            case QT_Q5_1: be = 32; bb = 24; break;
+            case QT_IQ4_NL: be = 32; bb = 18; break;
+            case QT_IQ4_XS: be = 256; bb = 136; break;
+            case QT_Q2_K: be = 256; bb = 84; break;
+            case QT_Q3_K: be = 256; bb = 110; break;
+            default: throw std::runtime_error("legacy_to_bf16: not a load-time expanded type");
+          }
+          py::buffer_info bi = raw.request();
+          const size_t nbytes = (size_t)bi.size * bi.itemsize;
+          if (n % be || nbytes != n / be * bb) throw std::runtime_error("legacy_to_bf16: byte size does not match n");
+          void* staging = nullptr;
+          HIP_CHECK(hipMalloc(&staging, nbytes));
+          HIP_CHECK(hipMemcpy(staging, bi.ptr, nbytes, hipMemcpyHostToDevice));
+          launch_legacy_to_bf16(qt, staging, n, (void*)out, S(st));
+          HIP_CHECK(hipStreamSynchronize(S(st)));
+          HIP_CHECK(hipFree(staging));
+        },
+        py::arg("qtype"), py::arg("raw_bytes"), py::arg("n"), py::arg("out_ptr"), py::arg("stream"));
   m.def("gemv",
         [](std::vector<PyQMatrix*> segs, int B, uintptr_t x, int ldx, uintptr_t norm_w, float eps, uintptr_t y,
            int ldy, int epi, uintptr_t st, int force_v1, int act_q8, int tune_grid, int tune_u, int tune_ksplit, int tune_dbg,
