@@ -321,7 +321,8 @@ PYBIND11_MODULE(_engine, m) {
       .def("decode_collect", &Engine::decode_collect, py::call_guard<py::gil_scoped_release>())
       .def("set_sample_processors", &Engine::set_sample_processors, py::arg("min_p"), py::arg("repeat_penalty"),
            py::arg("presence_penalty"), py::arg("frequency_penalty"), py::arg("recent"),
-           py::call_guard<py::gil_scoped_release>())
+           py::arg("bias_ids") = std::vector<std::vector<int>>{},
+           py::arg("bias_vals") = std::vector<std::vector<float>>{}, py::call_guard<py::gil_scoped_release>())
       .def("set_logprobs", &Engine::set_logprobs, py::arg("top_n"))
       .def("last_logprobs",
            [](const Engine& e) -> py::object {
@@ -770,7 +771,7 @@ PYBIND11_MODULE(_engine, m) {
         [](uintptr_t logits, int ldl, int B, int V, uintptr_t temperature, uintptr_t top_k, uint64_t seed,
            uintptr_t tokens, uintptr_t pos, uintptr_t mask, uintptr_t st, uintptr_t top_p, uintptr_t ts,
            uintptr_t min_p, uintptr_t pen_tokens, int pen_stride, uintptr_t repeat_penalty, uintptr_t presence_penalty,
-           uintptr_t frequency_penalty) {
+           uintptr_t frequency_penalty, uintptr_t bias_ids, uintptr_t bias_vals, int bias_stride) {
           // grow-on-demand scratch for the raw-op binding (the engine owns its own)
           static void* ws = nullptr;
           static size_t ws_bytes = 0;
@@ -798,12 +799,15 @@ PYBIND11_MODULE(_engine, m) {
           a.min_p = (const float*)min_p; a.pen_tokens = (const int*)pen_tokens; a.pen_stride = pen_stride;
           a.repeat_penalty = (const float*)repeat_penalty; a.presence_penalty = (const float*)presence_penalty;
           a.frequency_penalty = (const float*)frequency_penalty;
+          a.bias_ids = (const int*)bias_ids; a.bias_vals = (const float*)bias_vals; a.bias_stride = bias_stride;
           launch_sample(a, S(st));
         },
         py::arg("logits"), py::arg("ldl"), py::arg("B"), py::arg("V"), py::arg("temperature"), py::arg("top_k"),
         py::arg("seed"), py::arg("tokens"), py::arg("pos"), py::arg("mask"), py::arg("st"), py::arg("top_p") = 0,
         py::arg("ts") = 0, py::arg("min_p") = 0, py::arg("pen_tokens") = 0, py::arg("pen_stride") = 0,
-        py::arg("repeat_penalty") = 0, py::arg("presence_penalty") = 0, py::arg("frequency_penalty") = 0);
+        py::arg("repeat_penalty") = 0, py::arg("presence_penalty") = 0, py::arg("frequency_penalty") = 0,
+        py::arg("bias_ids") = 0, py::arg("bias_vals") = 0, py::arg("bias_stride") = 0);
+  m.attr("SAMPLE_BIAS_MAX") = SAMPLE_BIAS_MAX;
   m.attr("LOGPROB_MAX_TOP") = LOGPROB_MAX_TOP;
   m.def("logprobs",
         [](uintptr_t logits, int ldl, int B, int V, uintptr_t tokens, uintptr_t top_n, uintptr_t out_lp, uintptr_t out_id,

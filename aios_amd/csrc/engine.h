@@ -210,9 +210,15 @@ class Engine {
   // decode() with processors staged replays the forward graph and enqueues the sampler eagerly, like
   // the pipelined path (no graph of its own).  Single-GPU engines only: the ranks of a tensor-parallel
   // engine sample in lock step from arguments this call does not broadcast.
+  // bias_ids / bias_vals (both empty: none): the rows' logit-bias lists (ops.h, applied in front of the
+  // penalties), one list per row, at most SAMPLE_BIAS_MAX entries each, a row's ids distinct and in
+  // [0, vocab), a bias finite or -inf (a ban), fewer bans than the vocabulary has tokens; a row with an
+  // empty list is neutral.
   void set_sample_processors(const std::vector<float>& min_p, const std::vector<float>& repeat_penalty,
                              const std::vector<float>& presence_penalty, const std::vector<float>& frequency_penalty,
-                             const std::vector<std::vector<int>>& recent);
+                             const std::vector<std::vector<int>>& recent,
+                             const std::vector<std::vector<int>>& bias_ids = {},
+                             const std::vector<std::vector<float>>& bias_vals = {});
 
   // Per-token log-probabilities (ops.h LogprobArgs: the RAW distribution, before penalties, mask and
   // temperature) of the NEXT sampler launch only -- decode, decode_sample, sample_first or resample,
@@ -302,8 +308,9 @@ class Engine {
   // un-stages them (no-op when nothing is staged; throws when they were staged for another B)
   void take_processors(SampleArgs& s, int B);
   char* h_proc_ = nullptr;               // pinned staging: [4][max_batch] floats | [rows][stride] window ints
-  char* d_proc_ = nullptr;
+  char* d_proc_ = nullptr;               // | [rows][bias stride] bias ids | [rows][bias stride] bias floats
   int proc_rows_ = 0, proc_stride_ = 0;  // rows staged (0: none) and their window stride
+  int proc_bias_stride_ = 0;             // the staged rows' bias-list stride (0: no row has a bias)
   void take_logprobs(int B);             // after a B-row sampler launch: the staged logprob launch + its copy
   int lp_rows_ = 0;                      // rows staged by set_logprobs (0: none)
   // A sampler-launching call's hold on the staged logprobs, taken before it enqueues anything: refuses (and

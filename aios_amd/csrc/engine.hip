@@ -551,7 +551,8 @@ void Engine::finalize() {
     // queued (decode_submit); the other paths use the first half
     HIP_CHECK(hipHostMalloc(&h_par_, 2 * par_bytes_, hipHostMallocDefault));
     HIP_CHECK(hipHostMalloc((void**)&h_mask_, mb, hipHostMallocDefault));
-    const size_t pb = (size_t)Bm * (4 * 4 + (size_t)SAMPLE_PEN_MAX * 4);  // logit processors (set_sample_processors)
+    // logit processors (set_sample_processors): scalars, penalty windows, bias ids and values
+    const size_t pb = (size_t)Bm * (4 * 4 + (size_t)SAMPLE_PEN_MAX * 4 + (size_t)SAMPLE_BIAS_MAX * 8);
     HIP_CHECK(hipHostMalloc((void**)&h_proc_, pb, hipHostMallocDefault));
     d_proc_ = (char*)dmalloc(pb);
     ws += pb;
@@ -1166,7 +1167,9 @@ void Engine::enqueue_decode_forward(int B) {
 void Engine::set_sample_processors(const std::vector<float>& min_p, const std::vector<float>& repeat_penalty,
                                    const std::vector<float>& presence_penalty,
                                    const std::vector<float>& frequency_penalty,
-                                   const std::vector<std::vector<int>>& recent) {
+                                   const std::vector<std::vector<int>>& recent,
+                                   const std::vector<std::vector<int>>& bias_ids,
+                                   const std::vector<std::vector<float>>& bias_vals) {
   if (!finalized_) throw std::runtime_error("engine not finalized");
   if (cfg_.tp_size > 1) throw std::runtime_error("set_sample_processors: not available on a tensor-parallel engine");
   const int B = (int)recent.size(), Bm = cfg_.max_batch;
@@ -1182,6 +1185,33 @@ void Engine::set_sample_processors(const std::vector<float>& min_p, const std::v
       if (t < 0 || t >= cfg_.vocab_size) throw std::runtime_error("set_sample_processors: token out of range");
     stride = std::max(stride, (int)w.size());
   }
+  int bstride = 0;
+  if (!bias_ids.empty() || !bias_vals.empty()) {
+    if ((int)bias_ids.size() != B || (int)bias_vals.size() != B)
+      throw std::runtime_error("set_sample_processors: size mismatch");
+    std::vector<int> seen;
+    for (int b = 0; b < B; ++b) {
+      const auto& ids = bias_ids[b];
+      if (ids.size() != bias_vals[b].size()) throw std::runtime_error("set_sample_processors: size mismatch");
+      if ((int)ids.size() > SAMPLE_BIAS_MAX)
+        throw std::runtime_error("set_sample_processors: logit bias longer than " + std::to_string(SAMPLE_BIAS_MAX));
+      int bans = 0;
+      for (size_t j = 0; j < ids.size(); ++j) {
+        const float v = bias_vals[b][j];
+        if (ids[j] < 0 || ids[j] >= cfg_.vocab_size)
+          throw std::runtime_error("set_sample_processors: logit bias token out of range");
+        if (std::isnan(v) || (std::isinf(v) && v > 0.f))
+          throw std::runtime_error("set_sample_processors: logit bias must be finite or -inf");
+        bans += std::isinf(v) ? 1 : 0;
+      }
+      seen.assign(ids.begin(), ids.end());
+      std::sort(seen.begin(), seen.end());
+      if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+        throw std::runtime_error("set_sample_processors: duplicate logit bias token");
+      if (bans >= cfg_.vocab_size) throw std::runtime_error("set_sample_processors: logit bias bans every token");
+      bstride = std::max(bstride, (int)ids.size());
+    }
+  }
   // (one pinned buffer, h_mask_'s rule: the previous processors' copy ran before the sampler whose
   // token the host already collected -- the caller stages a step's processors from that token)
   float* hf = (float*)h_proc_;
@@ -1191,8 +1221,17 @@ void Engine::set_sample_processors(const std::vector<float>& min_p, const std::v
     hf[3 * Bm + b] = frequency_penalty[b];
     for (int j = 0; j < stride; ++j) hw[(size_t)b * stride + j] = j < (int)recent[b].size() ? recent[b][j] : -1;
   }
+  int* hb = hw + (size_t)B * stride;
+  float* hv = (float*)(hb + (size_t)B * bstride);
+  for (int b = 0; b < B && bstride; ++b)
+    for (int j = 0; j < bstride; ++j) {
+      const bool in = j < (int)bias_ids[b].size();
+      hb[(size_t)b * bstride + j] = in ? bias_ids[b][j] : -1;
+      hv[(size_t)b * bstride + j] = in ? bias_vals[b][j] : 0.f;
+    }
   proc_rows_ = B;
   proc_stride_ = stride;
+  proc_bias_stride_ = bstride;
 }
 
 void Engine::take_processors(SampleArgs& s, int B) {
@@ -1200,12 +1239,18 @@ void Engine::take_processors(SampleArgs& s, int B) {
   const int rows = proc_rows_, Bm = cfg_.max_batch;
   proc_rows_ = 0;  // one shot, also when the launch does not happen
   if (rows != B) throw std::runtime_error("sample processors staged for another batch size");
-  const size_t nbytes = (size_t)Bm * 16 + (size_t)B * proc_stride_ * 4;
+  const size_t wbytes = (size_t)Bm * 16 + (size_t)B * proc_stride_ * 4;
+  const size_t nbytes = wbytes + (size_t)B * proc_bias_stride_ * 8;
   HIP_CHECK(hipMemcpyAsync(d_proc_, h_proc_, nbytes, hipMemcpyHostToDevice, stream_));
   const float* df = (const float*)d_proc_;
   s.min_p = df; s.repeat_penalty = df + Bm; s.presence_penalty = df + 2 * Bm; s.frequency_penalty = df + 3 * Bm;
   s.pen_tokens = (const int*)(d_proc_ + (size_t)Bm * 16);
   s.pen_stride = proc_stride_;
+  if (proc_bias_stride_) {
+    s.bias_ids = (const int*)(d_proc_ + wbytes);
+    s.bias_vals = (const float*)(s.bias_ids + (size_t)B * proc_bias_stride_);
+    s.bias_stride = proc_bias_stride_;
+  }
 }
 
 void Engine::set_logprobs(const std::vector<int>& top_n) {

@@ -372,7 +372,9 @@ __device__ ArgMax block_argmax(ArgMax m, float* sv, int* si) {
 // without them): in A every slice workgroup counts the row's penalty window entries that fall in its
 // slice (an LDS table in s_ki, idle until the merge) and penalises its logits as it loads them, so the
 // slice argmax, the Gumbel path, the candidates and the merge's global max all see penalised logits;
-// min-p forces the candidate path and adds its ratio test to the merge's keep test.
+// min-p forces the candidate path and adds its ratio test to the merge's keep test.  The logit bias
+// (SampleArgs::bias_ids) works the same way in front of the penalties: the row's list entries inside the
+// slice are scattered into an LDS table in s_kv (idle until the merge too) and added at the load.
 // ----------------------------------------------------------------------------------------------
 #ifndef AIOS_SAMPLE_PROBES
 #define AIOS_SAMPLE_PROBES 0
@@ -485,6 +487,7 @@ __device__ __forceinline__ int block_excl_scan(int c, int* s_w, int& total) {
 }
 
 static_assert(SAMPLE_PEN_MAX <= SAMPLE_THREADS, "one penalty window entry per thread");
+static_assert(SAMPLE_BIAS_MAX <= 2 * SAMPLE_THREADS, "two bias entries per thread");
 static_assert(SAMPLE_MAX_V == 64 * SAMPLE_SLICE, "s_off holds 64 slices");
 template <bool PROC>
 __global__ void __launch_bounds__(SAMPLE_THREADS) sample_kernel(SampleArgs a) {
@@ -526,20 +529,35 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_kernel(SampleArgs a) {
   // ---- A) this slice in registers
   float v[SAMPLE_PER_THREAD];
   ArgMax m{-INFINITY, 0x7fffffff};
-  bool pen = false;
+  bool pen = false, bias = false;
   float rp = 1.f, pp = 0.f, fp = 0.f;
   if constexpr (PROC) {
     pen = a.pen_tokens != nullptr;
-    if (pen) {  // per-token counts of the window entries inside this slice (pen_stride <= SAMPLE_THREADS)
+    bias = a.bias_ids != nullptr;
+    if (pen || bias) {
+      // per-token counts of the window entries inside this slice (pen_stride <= SAMPLE_THREADS), and the
+      // bias of the list entries inside it (bias_stride <= 2 * SAMPLE_THREADS; -0 is the add's identity)
 #pragma unroll
-      for (int j = 0; j < SAMPLE_PER_THREAD; ++j) s_ki[j * SAMPLE_THREADS + tid] = 0;
+      for (int j = 0; j < SAMPLE_PER_THREAD; ++j) {
+        if (pen) s_ki[j * SAMPLE_THREADS + tid] = 0;
+        if (bias) s_kv[j * SAMPLE_THREADS + tid] = -0.f;
+      }
       __syncthreads();
-      if (tid < a.pen_stride) {
+      if (pen && tid < a.pen_stride) {
         const int t = a.pen_tokens[(size_t)b * a.pen_stride + tid];
         const int o = t - slice * SAMPLE_SLICE;
         if (t >= 0 && t < a.V && o >= 0 && o < SAMPLE_SLICE) atomicAdd(&s_ki[o], 1);
       }
+      if (bias) {  // (plain stores: a row's ids are distinct)
+        for (int e = tid; e < a.bias_stride; e += SAMPLE_THREADS) {
+          const int t = a.bias_ids[(size_t)b * a.bias_stride + e];
+          const int o = t - slice * SAMPLE_SLICE;
+          if (t >= 0 && t < a.V && o >= 0 && o < SAMPLE_SLICE) s_kv[o] = a.bias_vals[(size_t)b * a.bias_stride + e];
+        }
+      }
       __syncthreads();
+    }
+    if (pen) {
       if (a.repeat_penalty) rp = a.repeat_penalty[b];
       if (a.presence_penalty) pp = a.presence_penalty[b];
       if (a.frequency_penalty) fp = a.frequency_penalty[b];
@@ -551,6 +569,8 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) sample_kernel(SampleArgs a) {
     float x = -INFINITY;
     if (i < a.V && (!mask || ((mask[i >> 3] >> (i & 7)) & 1))) x = l[i];
     if constexpr (PROC) {
+      // (one rounding: the host's fp32 add; a masked token stays -inf, a -inf bias bans)
+      if (bias) x = __fadd_rn(x, s_kv[j * SAMPLE_THREADS + tid]);
       if (pen) {
         const int c = s_ki[j * SAMPLE_THREADS + tid];
         if (c > 0 && x > -INFINITY) {
@@ -810,8 +830,10 @@ void launch_sample(const SampleArgs& a, hipStream_t st) {
   if (a.ws_bytes < sample_ws_bytes(a.B, a.V)) throw std::runtime_error("sample: workspace too small");
   if (a.pen_tokens && (a.pen_stride < 1 || a.pen_stride > SAMPLE_PEN_MAX))
     throw std::runtime_error("sample: penalty window stride outside 1.." + std::to_string(SAMPLE_PEN_MAX));
+  if (a.bias_ids && (!a.bias_vals || a.bias_stride < 1 || a.bias_stride > SAMPLE_BIAS_MAX))
+    throw std::runtime_error("sample: logit bias stride outside 1.." + std::to_string(SAMPLE_BIAS_MAX));
   const dim3 grid(sample_slices(a.V), a.B);
-  if (a.min_p || a.pen_tokens) hipLaunchKernelGGL(sample_kernel<true>, grid, dim3(SAMPLE_THREADS), 0, st, a);
+  if (a.min_p || a.pen_tokens || a.bias_ids) hipLaunchKernelGGL(sample_kernel<true>, grid, dim3(SAMPLE_THREADS), 0, st, a);
   else hipLaunchKernelGGL(sample_kernel<false>, grid, dim3(SAMPLE_THREADS), 0, st, a);
 }
 

@@ -173,7 +173,17 @@ bool attn_prefill_supports(int n_heads, int n_kv_heads, int head_dim);  // keys 
 // to 256 * V / 4096) through its 4096-entry table in rounds (one round up to 4096 candidates, i.e. every
 // V <= 65536), in a fixed order: the same logits, settings and RNG key give the same token on every run.
 // tests/sampler_oracle.py is this rule in float64.
+// Logit bias (bias_ids non-null selects the processor instantiation too): per row a sparse list of at most
+// SAMPLE_BIAS_MAX entries (id, bias) -- ids distinct and in [0, V), -1 = empty entry, bias a finite fp32 or
+// -inf (a ban; +inf and NaN are refused by every layer that builds a list).  Order per row: bias, then the
+// penalties, then the mask, then everything above.  l[id] = l[id] + bias is ONE fp32 add (single rounding,
+// no contraction), so the penalty rule sees the biased logit, a masked token stays -inf whatever its bias,
+// and greedy argmax, the Gumbel path, the top-k threshold and its span, the nucleus and min-p's M all see
+// biased, penalised logits: the result is exactly what the sampler returns for logits to which the host
+// added the bias in fp32 beforehand.  runtime/sampler.py apply_logit_bias is the same rule on the host.
+// Logprobs and prompt scoring keep reporting the RAW distribution, before the bias.
 constexpr int SAMPLE_PEN_MAX = 256;  // longest penalty window (one entry per sampler thread)
+constexpr int SAMPLE_BIAS_MAX = 512; // longest logit-bias list (two entries per sampler thread)
 constexpr int SAMPLE_MAX_V = 262144; // largest vocabulary launch_sample takes (64 slices of 4096)
 struct SampleArgs {
   const float* logits;
@@ -203,6 +213,9 @@ struct SampleArgs {
   const float* frequency_penalty;  // [B] or null (0)
   const int* pen_tokens;           // [B][pen_stride] penalty windows, -1 = empty entry; or null
   int pen_stride;                  // <= SAMPLE_PEN_MAX
+  const int* bias_ids;             // [B][bias_stride] logit-bias ids, -1 = empty entry; or null (off)
+  const float* bias_vals;          // [B][bias_stride] their biases (finite or -inf)
+  int bias_stride;                 // <= SAMPLE_BIAS_MAX
 };
 void launch_sample(const SampleArgs& a, hipStream_t st);
 size_t sample_ws_bytes(int B, int V);

@@ -148,9 +148,12 @@ class CpuEngine:
             self.last = logits[-1][None]
         return host_scoring.score_rows(logits, [int(t) for t in ids[1:]] + [int(next_token)], top_n)
 
-    def set_sample_processors(self, min_p, repeat_penalty, presence_penalty, frequency_penalty, recent):
+    def set_sample_processors(self, min_p, repeat_penalty, presence_penalty, frequency_penalty, recent,
+                              bias_ids=(), bias_vals=()):
         """Per-row min-p, penalties and penalty windows (the rows' recent token ids) for the NEXT
-        sampler call (decode or sample_first), then dropped -- the native Engine's contract."""
+        sampler call (decode or sample_first), then dropped -- the native Engine's contract.
+        bias_ids / bias_vals: the rows' logit-bias lists (both empty: none), applied in front of the
+        penalties."""
         B = len(recent)
         if not (len(min_p) == len(repeat_penalty) == len(presence_penalty) == len(frequency_penalty) == B):
             raise ValueError("set_sample_processors: size mismatch")
@@ -160,8 +163,13 @@ class CpuEngine:
                 raise ValueError(f"set_sample_processors: window longer than {host_sampler.PEN_MAX}")
             if any(t >= V for t in w):
                 raise ValueError("set_sample_processors: token out of range")
+        if len(bias_ids) or len(bias_vals):
+            if len(bias_ids) != B or len(bias_vals) != B:
+                raise ValueError("set_sample_processors: size mismatch")
+            for ids, vals in zip(bias_ids, bias_vals):
+                host_sampler.check_logit_bias(ids, vals, V)
         self._proc = (list(min_p), list(repeat_penalty), list(presence_penalty), list(frequency_penalty),
-                      [list(w) for w in recent])
+                      [list(w) for w in recent], [list(i) for i in bias_ids], [list(v) for v in bias_vals])
 
     def set_logprobs(self, top_n):
         """Per-row alternatives wanted (0..LOGPROB_MAX_TOP, < 0: row off) from the NEXT sampler call
@@ -201,7 +209,9 @@ class CpuEngine:
     def _sample(self, proc, b, logits, t, k, tp, m, rng):
         if proc is None or b >= len(proc[4]):
             return host_sampler.sample(logits, t, k, tp, m, rng)
-        mp, rp, pp, fp, recent = proc
+        mp, rp, pp, fp, recent, bias_ids, bias_vals = proc
+        if bias_ids:
+            logits = host_sampler.apply_logit_bias(logits, bias_ids[b], bias_vals[b])
         logits = host_sampler.apply_penalties(logits, recent[b], rp[b], pp[b], fp[b])
         return host_sampler.sample(logits, t, k, tp, m, rng, min_p=float(mp[b]))
 

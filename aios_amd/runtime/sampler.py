@@ -4,8 +4,9 @@ Semantics match the device sampler (aios::sample_kernel): temperature <= 0 -> gr
 else sample from softmax(logits / T) restricted to the top-k (if k > 0) and nucleus top-p (if
 0 < p < 1), always within the grammar's allowed-token bitmask when one is given.
 
-Logit processors, in the device sampler's order: `apply_penalties` (repeat / presence / frequency
-over a window of the row's recent tokens, llama.cpp's rule) before the mask and everything else;
+Logit processors, in the device sampler's order: `apply_logit_bias` (a sparse list of (id, bias), one
+fp32 add each, -inf = ban) first, then `apply_penalties` (repeat / presence / frequency over a window
+of the row's recent tokens, llama.cpp's rule), both before the mask and everything else;
 min-p after top-k / top-p: a survivor stays only while exp((l - M) / T) >= min_p, M the largest
 allowed (penalised) logit -- a ratio test on the tempered distribution, so it intersects with the
 nucleus instead of renormalising before it.  Greedy ignores min-p.
@@ -46,6 +47,37 @@ def apply_penalties(logits: np.ndarray, recent: Sequence[int], repeat_penalty: f
     x = l[toks]
     x = np.where(x > 0, x / rp, x * rp).astype(np.float32)
     l[toks] = x - (cnt.astype(np.float32) * fp + pp)
+    return l
+
+
+BIAS_MAX = 512  # longest logit-bias list (the device sampler reads two list entries per thread)
+
+
+def check_logit_bias(ids: Sequence[int], vals: Sequence[float], vocab: int) -> None:
+    """ValueError unless (ids, vals) is a list the sampler takes: at most BIAS_MAX entries, ids distinct
+    and in [0, vocab), every bias a finite number or -inf, fewer bans than the vocabulary has tokens"""
+    if len(ids) != len(vals):
+        raise ValueError("logit_bias: size mismatch")
+    if len(ids) > BIAS_MAX:
+        raise ValueError(f"logit_bias: more than {BIAS_MAX} entries")
+    if any(not 0 <= int(t) < vocab for t in ids):
+        raise ValueError("logit_bias: token out of range")
+    if len(set(int(t) for t in ids)) != len(ids):
+        raise ValueError("logit_bias: duplicate token")
+    if any(np.isnan(v) or v == np.inf for v in vals):
+        raise ValueError("logit_bias: bias must be finite or -inf")
+    if sum(1 for v in vals if v == -np.inf) >= vocab:
+        raise ValueError("logit_bias: every token banned")
+
+
+def apply_logit_bias(logits: np.ndarray, ids: Sequence[int], vals: Sequence[float]) -> np.ndarray:
+    """Biased copy of `logits`: l[id] = l[id] + bias, one fp32 add per entry (the device sampler's
+    operation); entries with id < 0 are empty, a -inf bias bans the token.  Applied in front of
+    `apply_penalties`, which then sees the biased logit."""
+    l = np.array(logits, dtype=np.float32)
+    for t, v in zip(ids, vals):
+        if 0 <= int(t) < l.shape[0]:
+            l[int(t)] = l[int(t)] + np.float32(v)
     return l
 
 

@@ -69,6 +69,13 @@ class GenRequest:
     repeat_last_n: int = 64           # penalty window: the row's last n tokens, prompt tail included (< 0 or > 256: 256)
     presence_penalty: Optional[float] = None
     frequency_penalty: Optional[float] = None
+    # logit bias (runtime/sampler.py: apply_logit_bias, in front of the penalties): token id -> a finite bias
+    # or -inf (a ban), at most 512 entries.  ignore_eos bans the tier's end-of-sequence ids (over a finite
+    # bias on them): the request ends by max_tokens, its other stop ids or the context window.  In JSON mode
+    # the grammar wins: at a step where no token is both allowed by the grammar and unbanned, the bans are
+    # left out for that step (stats["bias_overridden"])
+    logit_bias: Optional[Dict[int, float]] = None
+    ignore_eos: bool = False
     # per-token log-probabilities of the model's RAW distribution (before penalties, the grammar mask and
     # temperature; runtime/sampler.py: logprobs): the chosen token's, and its top_logprobs (0..20) best
     # alternatives -- GenResult.logprobs.  The stream callback carries text only.
@@ -131,7 +138,7 @@ SPEC_DEFAULTS = dict(mode="off", draft_max=7, ngram_min=2, ngram_max=3, max_cont
 
 class _Seq:
     __slots__ = ("req", "slot", "pos", "last", "out", "grammar_state", "emitted", "t_first", "cached", "todo",
-                 "p_off", "r_off", "seed", "proc", "pen_n", "lp_n", "lps", "embedding", "plp_n", "plps",
+                 "p_off", "r_off", "seed", "proc", "pen_n", "bias", "bias_soft", "lp_n", "lps", "embedding", "plp_n", "plps",
                  "spec", "drafter", "drafted", "draft_hits")
 
     def __init__(self, req, slot):
@@ -149,6 +156,8 @@ class _Seq:
         self.todo: List[int] = []    # prompt tokens still to prefill
         self.proc = None             # (min_p, repeat, presence, frequency penalty), None when all neutral
         self.pen_n = 0               # penalty window length
+        self.bias = None             # logit bias (ids, vals), built once at admission; None when empty
+        self.bias_soft = None        # the same without its -inf entries (a step where the grammar wins)
         self.lp_n = int(req.top_logprobs) if req.logprobs else -1  # alternatives per token; -1: no logprobs
         self.lps: List[tuple] = []   # one entry per token of `out`
         self.embedding = None        # an embedding request's result
@@ -189,6 +198,8 @@ class Scheduler:
                 raise ValueError(f"unknown sampling default {k!r}")
             self.sampling_defaults[k] = float(v)
         self._warned_no_processors = False
+        # a logit bias needs the engine's set_sample_processors (a tensor-parallel tier hides the call)
+        self.can_bias = hasattr(engine, "set_sample_processors")
         # per-token logprobs need the engine's set_logprobs / last_logprobs (a tensor-parallel tier has
         # neither: its lm_head is vocab-parallel)
         self.can_logprobs = hasattr(engine, "set_logprobs") and hasattr(engine, "last_logprobs")
@@ -221,7 +232,8 @@ class Scheduler:
         self.cv = threading.Condition()
         self.stop_flag = False
         self.stats = dict(requests=0, tokens=0, prefill_tokens=0, cached_tokens=0, steps=0, batch_sum=0, errors=0,
-                          embeddings=0, prompt_scores=0, spec_steps=0, spec_drafted=0, spec_accepted=0)
+                          embeddings=0, prompt_scores=0, spec_steps=0, spec_drafted=0, spec_accepted=0,
+                          bias_overridden=0)
         # health / metrics (ModelManager.supervise and HealthCheck details)
         self.max_slots = max_slots
         self.last_progress = time.time()   # last completed admission or decode step
@@ -404,6 +416,7 @@ class Scheduler:
                 raise ValueError(f"top_logprobs outside 0..{host_sampler.LOGPROB_MAX_TOP}")
             if not self.can_logprobs:
                 raise ValueError(f"{self.name}: this tier's engine cannot report logprobs")
+        bias = self._bias_of(r)
         r.max_tokens = max(0 if score else 1, min(r.max_tokens, self.max_ctx - len(ids)))
         r.min_tokens = min(r.min_tokens, r.max_tokens)
         if score:  # cached positions have no logits to score: from position 0, in the least useful slot
@@ -419,6 +432,10 @@ class Scheduler:
         if proc != tuple(NEUTRAL_PROCESSORS.values()):
             seq.proc = proc
             seq.pen_n = host_sampler.penalty_window(r.repeat_last_n)
+        if bias is not None:
+            seq.bias = bias
+            keep = [j for j, v in enumerate(bias[1]) if v != -np.inf]
+            seq.bias_soft = ([bias[0][j] for j in keep], [bias[1][j] for j in keep])
         seq.spec = self.spec["mode"] == "lookup" if r.speculative is None else bool(r.speculative)
         if seq.spec and not self.can_spec:
             seq.spec = False
@@ -426,6 +443,45 @@ class Scheduler:
                 self._warned_no_spec = True
                 log.warning("%s: the engine has no spec_decode; speculative decoding is off on this tier", self.name)
         self._begin_prefill(seq, common)
+
+    def _bias_of(self, r: GenRequest):
+        """The request's logit-bias list (ids, vals), or None when it has none; ValueError for a list the
+        sampler does not take or a tier that cannot apply one (a ban silently dropped is worse than a
+        refusal: unlike the penalties, which such a tier ignores with a log line)."""
+        bias = {}
+        for t, v in (r.logit_bias or {}).items():
+            if isinstance(t, bool) or not isinstance(t, (int, np.integer)):
+                raise ValueError("logit_bias: token ids must be integers")
+            bias[int(t)] = float(v)
+        if r.ignore_eos:
+            for t in self.eos:
+                bias[int(t)] = -np.inf
+        if not bias:
+            return None
+        ids, vals = list(bias), list(bias.values())
+        host_sampler.check_logit_bias(ids, vals, self.vocab)
+        if not self.can_bias:
+            raise ValueError(f"{self.name}: logit_bias: single-GPU engines only")
+        return ids, vals
+
+    def _bias_lists(self, rows, masks: bytes = b""):
+        """The rows' bias lists for one sampler launch (masks: the launch's grammar masks, b"" for none).
+        The grammar wins: a row whose mask allows no unbanned token gets its list without the bans for
+        this step, so the sampler never sees a row with nothing left."""
+        nb = (self.vocab + 7) // 8
+        ids, vals = [], []
+        for b, s in enumerate(rows):
+            bias = s.bias or ((), ())
+            if s.bias is not None and masks and s.grammar_state is not None and len(s.bias_soft[0]) < len(bias[0]):
+                m = masks[b * nb:(b + 1) * nb]
+                allowed = int.from_bytes(m, "little").bit_count()
+                hit = sum(1 for t, v in zip(*bias) if v == -np.inf and (m[t >> 3] >> (t & 7)) & 1)
+                if allowed and hit >= allowed:
+                    bias = s.bias_soft
+                    self.stats["bias_overridden"] += 1
+            ids.append(list(bias[0]))
+            vals.append(list(bias[1]))
+        return ids, vals
 
     def _prefill_chunk(self, seq: _Seq, whole: bool = False):
         """Prefill the next chunk of seq's prompt; the last chunk samples the first token and
@@ -475,7 +531,7 @@ class Scheduler:
         topp = float(r.top_p) if 0.0 < r.top_p < 1.0 else 1.0
         if hasattr(self.engine, "sample_first"):
             # on the device, the decode steps' sampler and RNG stream (seed, position)
-            self._processors([seq])
+            self._processors([seq], bytes(mask) if mask is not None else b"")
             self._stage_logprobs([seq])
             tok = int(self.engine.sample_first(seq.pos - 1, float(r.temperature), topk, topp, seq.seed,
                                                bytes(mask) if mask is not None else b""))
@@ -484,6 +540,9 @@ class Scheduler:
             rng = np.random.default_rng([seq.seed & 0xFFFFFFFF, seq.pos - 1])
             min_p = 0.0
             raw = logits
+            if seq.bias is not None:
+                bi, bv = self._bias_lists([seq], bytes(mask) if mask is not None else b"")
+                logits = host_sampler.apply_logit_bias(logits, bi[0], bv[0])
             if seq.proc is not None:
                 min_p = seq.proc[0]
                 logits = host_sampler.apply_penalties(logits, self._window(seq), *seq.proc[1:])
@@ -655,10 +714,12 @@ class Scheduler:
         out = s.out + list(extra) if extra else s.out
         return (s.req.prompt_ids[-(n - len(out)):] if len(out) < n else []) + out[-n:]
 
-    def _processors(self, rows):
+    def _processors(self, rows, masks: bytes = b""):
         """Before a sampler launch: hand the engine the rows' min-p / penalties and penalty windows
-        (every token of a row is on the host at this point).  All rows neutral: no call at all."""
-        if not any(s.proc is not None for s in rows):
+        (every token of a row is on the host at this point) and their logit-bias lists (masks: the
+        launch's grammar masks, for _bias_lists).  All rows neutral: no call at all."""
+        biased = any(s.bias is not None for s in rows)
+        if not biased and not any(s.proc is not None for s in rows):
             return
         setp = getattr(self.engine, "set_sample_processors", None)
         if setp is None:
@@ -668,8 +729,11 @@ class Scheduler:
             return
         neutral = tuple(NEUTRAL_PROCESSORS.values())
         cols = list(zip(*[s.proc or neutral for s in rows]))
-        setp(list(cols[0]), list(cols[1]), list(cols[2]), list(cols[3]),
-             [self._window(s) if s.proc is not None else [] for s in rows])
+        windows = [self._window(s) if s.proc is not None else [] for s in rows]
+        if biased:
+            setp(list(cols[0]), list(cols[1]), list(cols[2]), list(cols[3]), windows, *self._bias_lists(rows, masks))
+        else:
+            setp(list(cols[0]), list(cols[1]), list(cols[2]), list(cols[3]), windows)
 
     def _stage_logprobs(self, rows):
         """Before a sampler launch, after _processors: the rows' top_logprobs for the engine's logprob
@@ -708,9 +772,10 @@ class Scheduler:
         if rows is None:  # a batch's first step (or after an admission / finish): host tokens
             rows = list(self.active)
             self._submit(rows, True)
-            self._processors(rows)
+            masks = self._masks(rows)
+            self._processors(rows, masks)
             self._stage_logprobs(rows)
-            self.engine.decode_sample(self._masks(rows))
+            self.engine.decode_sample(masks)
         self._pending = None
         spec = self._can_speculate(rows)
         if spec:
@@ -722,9 +787,10 @@ class Scheduler:
         t2b = time.perf_counter()
         if spec and self.active == rows:
             # nobody finished or joined: sample the queued forward with the masks of the new tokens
-            self._processors(rows)
+            masks = self._masks(rows)
+            self._processors(rows, masks)
             self._stage_logprobs(rows)
-            self.engine.decode_sample(self._masks(rows))
+            self.engine.decode_sample(masks)
             self._pending = rows
         # (spec and a row finished: the queued forward is dropped -- its KV writes at the next
         # position are rewritten by whatever runs there next)
@@ -787,9 +853,14 @@ class Scheduler:
         if not draft:
             return False
         r, R = s.req, len(draft) + 1
-        if s.proc is not None and hasattr(self.engine, "set_sample_processors"):
-            self.engine.set_sample_processors(*[[v] * R for v in s.proc], [self._window(s, draft[:i]) for i in range(R)])
         rows = [s] * R
+        if s.bias is not None:  # the same list on each of the R rows (the grammar-wins test is per row's mask)
+            proc = s.proc or tuple(NEUTRAL_PROCESSORS.values())
+            self.engine.set_sample_processors(*[[v] * R for v in proc],
+                                              [self._window(s, draft[:i]) if s.proc is not None else [] for i in range(R)],
+                                              *self._bias_lists(rows, masks))
+        elif s.proc is not None and hasattr(self.engine, "set_sample_processors"):
+            self.engine.set_sample_processors(*[[v] * R for v in s.proc], [self._window(s, draft[:i]) for i in range(R)])
         self._stage_logprobs(rows)
         t1 = time.perf_counter()
         acc, out = self.engine.spec_decode(s.slot, [s.last] + draft, s.pos, float(r.temperature),
@@ -840,7 +911,7 @@ class Scheduler:
             mask = b"".join(self._mask(s) if s.grammar_state is not None else self._full_mask for s in self.active)
         topp = [float(s.req.top_p) if 0.0 < s.req.top_p < 1.0 else 1.0 for s in self.active]
         rows = list(self.active)
-        self._processors(rows)
+        self._processors(rows, mask)
         self._stage_logprobs(rows)
         t1 = time.perf_counter()
         out = self.engine.decode(slots, toks, pos, temps, topk, 0, mask, topp, seeds)

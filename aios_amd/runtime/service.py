@@ -16,6 +16,7 @@ from __future__ import annotations
 import asyncio
 import json
 import logging
+import math
 import os
 import time
 from typing import Dict, List, Optional
@@ -27,7 +28,7 @@ from ..rpc.schema import pb
 from .chat_template import build_messages
 from .embedding import MAX_INPUTS as MAX_EMBED_INPUTS
 from .model_manager import ModelManager, RoutingError
-from .sampler import LOGPROB_MAX_TOP
+from .sampler import BIAS_MAX, LOGPROB_MAX_TOP
 from .scheduler import GenRequest, GenResult
 
 log = logging.getLogger("aios.runtime.service")
@@ -85,6 +86,55 @@ def logprobs_from_body(body: dict, scheduler) -> Optional[int]:
     if not getattr(scheduler, "can_logprobs", False):  # (a tensor-parallel tier: vocab-parallel lm_head)
         raise ValueError("this model's engine cannot report logprobs")
     return int(top or 0)
+
+
+def bias_from_body(body: dict, scheduler):
+    """`logit_bias` and `ignore_eos` of a chat or completions body: (GenRequest.logit_bias, GenRequest.ignore_eos).
+    logit_bias: OpenAI's map {"<token id>": number} or llama-server's list [[id, number | false], ...] (false:
+    a ban, as -inf is); values outside OpenAI's [-100, 100] are taken as they are.  ValueError (-> 400) for a
+    malformed field and on a tier whose engine cannot apply one (a tensor-parallel tier)."""
+    raw, ieos = body.get("logit_bias"), body.get("ignore_eos")
+    if ieos is not None and not isinstance(ieos, bool):
+        raise ValueError("ignore_eos must be a boolean")
+    if raw is None and not ieos:  # (a body without the fields asks nothing of the tier)
+        return None, False
+    vocab = scheduler.vocab
+    bias = {}
+
+    def entry(tid, v):
+        if isinstance(tid, str):
+            try:
+                tid = int(tid.strip())
+            except ValueError:
+                raise ValueError(f"logit_bias: key {tid!r} is not an integer token id") from None
+        if isinstance(tid, bool) or not isinstance(tid, int) or not 0 <= tid < vocab:
+            raise ValueError(f"logit_bias: token id {tid!r} outside [0, {vocab})")
+        if v is False:
+            v = -math.inf
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"logit_bias: the bias of token {tid} must be a number (or false: a ban)")
+        v = float(v)
+        if v != v or v == math.inf:
+            raise ValueError(f"logit_bias: the bias of token {tid} must be finite or -inf")
+        if tid in bias:
+            raise ValueError(f"logit_bias: duplicate token id {tid}")
+        bias[tid] = v
+
+    if isinstance(raw, dict):
+        for k, v in raw.items():
+            entry(k, v)
+    elif isinstance(raw, list):
+        for it in raw:
+            if not isinstance(it, (list, tuple)) or len(it) != 2 or isinstance(it[0], str):
+                raise ValueError("logit_bias: the list form takes [token id, bias] pairs")
+            entry(it[0], it[1])
+    elif raw is not None:
+        raise ValueError("logit_bias must be a map of token ids to biases or a list of [token id, bias] pairs")
+    if len(bias) > BIAS_MAX:
+        raise ValueError(f"logit_bias: more than {BIAS_MAX} entries")
+    if (bias or ieos) and not getattr(scheduler, "can_bias", False):
+        raise ValueError("logit_bias: single-GPU engines only" if bias else "ignore_eos: single-GPU engines only")
+    return (bias or None), bool(ieos)
 
 
 def prediction_from_body(body: dict, tokenizer):
@@ -230,7 +280,8 @@ def completion_request(body: dict, tokenizer, scheduler) -> dict:
     except (TypeError, ValueError) as e:
         raise ValueError(f"bad sampling field: {e}") from None
     speculative, prediction_ids = prediction_from_body(body, tokenizer)
-    return dict(ids=ids, prompt_text=text, max_tokens=int(max_tokens), temperature=max(temperature, 0.0),
+    logit_bias, ignore_eos = bias_from_body(body, scheduler)
+    return dict(logit_bias=logit_bias, ignore_eos=ignore_eos, ids=ids, prompt_text=text, max_tokens=int(max_tokens), temperature=max(temperature, 0.0),
                 echo=bool(echo), logprobs=lp, stream=stream, sampling=sampling, repeat_last_n=rln,
                 speculative=speculative, prediction_ids=prediction_ids)
 
@@ -289,6 +340,7 @@ async def complete(m, c: dict, on_delta=None, timeout: float = 120.0) -> GenResu
         if c["echo"]:
             req.prompt_logprobs = int(c["logprobs"])
     req.speculative, req.prediction_ids = c.get("speculative"), c.get("prediction_ids")
+    req.logit_bias, req.ignore_eos = c.get("logit_bias"), bool(c.get("ignore_eos"))
     m.scheduler.submit(req)
     try:
         return await asyncio.wait_for(fut, timeout + 5)
@@ -320,10 +372,12 @@ async def embed(m, inputs: List[List[int]], pooling: str, timeout: float = 120.0
 async def generate(m, messages, max_tokens: int, temperature: float, json_mode: bool, on_delta=None,
                    timeout: float = 120.0, seed: int = 0, sampling: Optional[dict] = None,
                    top_logprobs: Optional[int] = None, speculative: Optional[bool] = None,
-                   prediction_ids: Optional[List[int]] = None) -> GenResult:
+                   prediction_ids: Optional[List[int]] = None, logit_bias: Optional[Dict[int, float]] = None,
+                   ignore_eos: bool = False) -> GenResult:
     """sampling: further GenRequest fields by name (top_p, top_k, seed, min_p, the penalties);
     top_logprobs: None, or per-token logprobs with that many alternatives (GenResult.logprobs);
-    speculative / prediction_ids: GenRequest's (prediction_from_body)"""
+    speculative / prediction_ids: GenRequest's (prediction_from_body); logit_bias / ignore_eos:
+    GenRequest's (bias_from_body)"""
     loop = asyncio.get_running_loop()
     fut = loop.create_future()
     prompt = m.template.render(messages, add_generation_prompt=True)
@@ -345,6 +399,7 @@ async def generate(m, messages, max_tokens: int, temperature: float, json_mode: 
     if top_logprobs is not None:
         req.logprobs, req.top_logprobs = True, int(top_logprobs)
     req.speculative, req.prediction_ids = speculative, prediction_ids
+    req.logit_bias, req.ignore_eos = logit_bias, ignore_eos
     m.scheduler.submit(req)
     try:
         return await asyncio.wait_for(fut, timeout + 5)
@@ -521,6 +576,7 @@ class AIRuntimeService:
         try:
             top_logprobs = logprobs_from_body(body, m.scheduler)
             speculative, prediction_ids = prediction_from_body(body, m.tokenizer)
+            logit_bias, ignore_eos = bias_from_body(body, m.scheduler)
         except ValueError as e:
             return web.json_response({"error": {"message": str(e), "type": "invalid_request_error"}}, status=400)
         created = int(time.time())
@@ -531,7 +587,8 @@ class AIRuntimeService:
             q: asyncio.Queue = asyncio.Queue()
             task = asyncio.ensure_future(generate(m, messages, max_tokens, temperature, json_mode, on_delta=q.put_nowait,
                                                   sampling=sampling, speculative=speculative,
-                                                  prediction_ids=prediction_ids))
+                                                  prediction_ids=prediction_ids, logit_bias=logit_bias,
+                                                  ignore_eos=ignore_eos))
             task.add_done_callback(lambda _t: q.put_nowait(None))
             while True:
                 d = await q.get()
@@ -547,7 +604,8 @@ class AIRuntimeService:
             await resp.write_eof()
             return resp
         res = await generate(m, messages, max_tokens, temperature, json_mode, sampling=sampling,
-                             top_logprobs=top_logprobs, speculative=speculative, prediction_ids=prediction_ids)
+                             top_logprobs=top_logprobs, speculative=speculative, prediction_ids=prediction_ids,
+                             logit_bias=logit_bias, ignore_eos=ignore_eos)
         choice = {"index": 0, "message": {"role": "assistant", "content": res.text},
                   "finish_reason": "length" if res.finish_reason == "length" else "stop"}
         if top_logprobs is not None:  # (bodies of requests that did not ask stay as they were)
