@@ -205,8 +205,10 @@ class Engine {
 
   // Logit processors (ops.h SampleArgs: min-p, repeat / presence / frequency penalties) of the NEXT
   // sampler launch only -- decode, decode_sample, sample_first or resample, whichever comes first --
-  // and dropped after it, so a row's values never reach another batch.  One entry per row of that
-  // launch; recent[b]: the row's penalty window, at most SAMPLE_PEN_MAX token ids, each in [0, vocab).
+  // and dropped after it, so a row's values never reach another batch.  Dropped as well by a sampler-launching
+  // call that throws before its launch (a refused argument, say) and by decode_loop_run: they never wait
+  // for a later, unrelated launch with the same row count.  One entry per row of that launch; recent[b]:
+  // the row's penalty window, at most SAMPLE_PEN_MAX token ids, each in [0, vocab).
   // decode() with processors staged replays the forward graph and enqueues the sampler eagerly, like
   // the pipelined path (no graph of its own).  Single-GPU engines only: the ranks of a tensor-parallel
   // engine sample in lock step from arguments this call does not broadcast.
@@ -298,14 +300,20 @@ class Engine {
   uintptr_t kv_cache_v() const { return (uintptr_t)v_cache_; }
 
  private:
-  void enqueue_decode_step(int B);       // uses device arrays d_tokens_/d_pos_/d_seqlen_/d_slot_
-  void enqueue_decode_forward(int B);    // ... up to the logits (no sampler)
-  void enqueue_sample(int B, bool processors = false);  // the step's sampler (sample_mask_: with d_mask_)
+  void enqueue_decode_step(int B, bool masked);  // uses device arrays d_tokens_/d_pos_/d_seqlen_/d_slot_
+  void enqueue_decode_forward(int B);            // ... up to the logits (no sampler)
   // what every sampler launch shares: logits_, the parameter block's row arrays, workspace and tickets
-  // (mask: d_mask_ or null); the caller adds its seed source, pos and advance
+  // (mask: d_mask_ or null)
   SampleArgs sample_args(int B, bool masked) const;
+  // the fields the launches differ in -- STEP (decode, decode_sample, spec_decode): the device seed, d_pos_,
+  // sequence lengths and history, advancing; AGAIN (resample): the device seed and d_pos_, no advance; FIRST
+  // (sample_first): d_fpos_ and the row seed alone, no advance
+  enum SampleKind { SAMPLE_STEP, SAMPLE_AGAIN, SAMPLE_FIRST };
+  // THE sampler launch.  staged: the staged processors go in front of it and the staged logprob launch
+  // behind it; the captured step graph passes false and holds the sampler alone
+  void enqueue_sample(int B, bool masked, SampleKind kind = SAMPLE_STEP, bool staged = false);
   // the staged logit processors of a B-row sampler launch: uploads them, points s at them and
-  // un-stages them (no-op when nothing is staged; throws when they were staged for another B)
+  // un-stages them (no-op when nothing is staged)
   void take_processors(SampleArgs& s, int B);
   char* h_proc_ = nullptr;               // pinned staging: [4][max_batch] floats | [rows][stride] window ints
   char* d_proc_ = nullptr;               // | [rows][bias stride] bias ids | [rows][bias stride] bias floats
@@ -313,28 +321,19 @@ class Engine {
   int proc_bias_stride_ = 0;             // the staged rows' bias-list stride (0: no row has a bias)
   void take_logprobs(int B);             // after a B-row sampler launch: the staged logprob launch + its copy
   int lp_rows_ = 0;                      // rows staged by set_logprobs (0: none)
-  // A sampler-launching call's hold on the staged logprobs, taken before it enqueues anything: refuses (and
-  // drops) a staging made for another batch size, and drops the staging when the call ends, however it
-  // ends -- a call that throws half way never leaves it to a later, unrelated launch.
-  struct LogprobStage {
-    int& rows;
-    LogprobStage(int& staged, int B, const char* who) : rows(staged) {
-      if (rows && rows != B) {
-        rows = 0;
-        throw std::runtime_error(std::string(who) + ": logprobs staged for another batch size");
-      }
+  // A sampler-launching call's hold on the staged processors and logprobs, taken before it changes any
+  // state: refuses (and drops both) when either was staged for another batch size, and drops both when the
+  // call ends, however it ends -- a call that throws half way never leaves them to a later, unrelated launch.
+  struct SampleStage {
+    Engine& e;
+    SampleStage(Engine& eng, int B, const char* who) : e(eng) {
+      const char* bad = e.proc_rows_ && e.proc_rows_ != B ? "sample processors"
+                        : e.lp_rows_ && e.lp_rows_ != B   ? "logprobs" : nullptr;
+      if (!bad) return;
+      e.proc_rows_ = e.lp_rows_ = 0;
+      throw std::runtime_error(std::string(who) + ": " + bad + " staged for another batch size");
     }
-    ~LogprobStage() { rows = 0; }
-  };
-  // Its twin for the staged logit processors: the same refusal.  No destructor: take_processors drops the
-  // staging at the sampler launch, and a call that throws before that launch keeps it, as it always did.
-  struct ProcessorStage {
-    ProcessorStage(int& staged, int B, const char* who) {
-      if (staged && staged != B) {
-        staged = 0;
-        throw std::runtime_error(std::string(who) + ": sample processors staged for another batch size");
-      }
-    }
+    ~SampleStage() { e.proc_rows_ = e.lp_rows_ = 0; }
   };
   std::vector<int> lp_last_;             // top_n of the rows the last sampler launch reported (empty: none)
   char* h_lp_ = nullptr;                 // pinned: [max_batch] top_n | the device output block's mirror
@@ -452,11 +451,35 @@ class Engine {
   enum { PAR_SLOT, PAR_TOKEN, PAR_POS, PAR_SEQLEN, PAR_TOPK, PAR_TEMP, PAR_TOPP, PAR_ROWS };
   size_t par_off(int array) const { return 8 + (size_t)array * cfg_.max_batch * 4; }
   size_t par_seeds_off_ = 0;
-  // a step's rows into the pinned block at hpar (tokens empty: that array is left alone)
+  char* next_par() { return h_par_ + (size_t)(par_buf_ ^= 1) * par_bytes_; }  // flips to the other pinned half
+  void par_copy(const char* hpar, size_t from, size_t to);  // bytes [from, to) of that half to the device block
+  // decode's and decode_submit's checks of a step's rows (tokens may be empty only when !need_tokens)
+  void check_step(const std::string& who, const std::vector<int>& slots, const std::vector<int>& tokens,
+                  const std::vector<int>& pos, const std::vector<uint64_t>& seeds, bool need_tokens) const;
+  // B rows' sampling parameters into the pinned block at hpar: the seed, top_k / temperature / top_p (missing
+  // entries: 0 / 0 / 1) and the row seeds
+  void write_sample_params(char* hpar, int B, const std::vector<float>& temperature, const std::vector<int>& top_k,
+                           const std::vector<float>& top_p, uint64_t seed, const std::vector<uint64_t>& seeds);
+  // those and a step's rows (tokens empty: that array is left alone)
   void write_step_params(char* hpar, const std::vector<int>& slots, const std::vector<int>& tokens,
                          const std::vector<int>& pos, const std::vector<float>& temperature,
                          const std::vector<int>& top_k, const std::vector<float>& top_p, uint64_t seed,
                          const std::vector<uint64_t>& seeds);
+  // a step's upload: write_step_params into the next pinned half, the mask behind it when there is one, one
+  // copy (tokens empty: two, around the array the last sampler left on the device)
+  void upload_step_params(const std::vector<int>& slots, const std::vector<int>& tokens, const std::vector<int>& pos,
+                          const std::vector<float>& temperature, const std::vector<int>& top_k,
+                          const std::vector<float>& top_p, uint64_t seed, const std::vector<uint64_t>& seeds,
+                          const std::vector<uint8_t>& mask = {});
+  // a sampler-only call's upload (resample, sample_first): write_sample_params into the next pinned half, one
+  // copy of top_k .. top_p (up to row B of top_p), one of the row seeds, one of the seed when dev_seed -- never
+  // slot / token / pos / seq_len, which a pipelined decode_submit(tokens = {}) continues from
+  void upload_sample_params(int B, const std::vector<float>& temperature, const std::vector<int>& top_k,
+                            const std::vector<float>& top_p, uint64_t seed, const std::vector<uint64_t>& seeds,
+                            bool dev_seed);
+  // map (and un-share) the blocks the B rows' next n positions write, before anything that writes them is
+  // enqueued, and move the rows' host positions there
+  void advance_rows(int B, int n);
   void gemv(const std::vector<const QMat*>& segs, int N, int K, int B, const float* x, int ldx, const float* norm_w,
             float* y, int ldy, int epi, int layer);
   GemvArgs gemv_args(const std::vector<const QMat*>& segs, int N, int K, int B, const float* x, int ldx,
@@ -577,7 +600,8 @@ class Engine {
   bool nrm_on(int B) const;
   bool tpn_on(int B) const;  // batched TP decode: C1 / C2 fused with the next RMSNorm
   void layer_decode_gemm(int l, int B);
-  hipGraphExec_t step_graph(int B);
+  hipGraphExec_t step_graph(int B, bool masked);
+  void decode_loop_body(int B, int n_steps, bool use_graph, bool masked);  // decode_loop_run, with the steps' mask flag
   bool nrm_lm_ = false;  // the last layer's down GEMM prepared dec_xn16_ / nrm_part_ for lm_head(x_)
   int *pf_tokens_ = nullptr, *pf_pos_ = nullptr, *pf_seqlen_ = nullptr, *pf_slot_ = nullptr;
 
@@ -611,10 +635,6 @@ class Engine {
   float* tpn_part_ = nullptr;
   SplitNorm lm_nrm_{};  // the split-norm operands the lm_head consumes when nrm_lm_ is set (nrm_part_ or tpn_part_)
   void* allgather_ctx_ = nullptr;
-  // sampling config for the enqueued step
-  bool sample_temp_ = false;
-  bool sample_mask_ = false;
-  uint64_t sample_seed_ = 0;
 };
 
 }  // namespace aios

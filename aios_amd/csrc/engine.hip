@@ -548,7 +548,7 @@ void Engine::finalize() {
     d_par_ = (char*)dmalloc(par_bytes_);
     ws += par_bytes_;
     // two halves: the pipelined decode writes step t+1's parameters while step t's copy may still be
-    // queued (decode_submit); the other paths use the first half
+    // queued (decode_submit); every upload through the block writes the half the last one did not (next_par)
     HIP_CHECK(hipHostMalloc(&h_par_, 2 * par_bytes_, hipHostMallocDefault));
     HIP_CHECK(hipHostMalloc((void**)&h_mask_, mb, hipHostMallocDefault));
     // logit processors (set_sample_processors): scalars, penalty windows, bias ids and values
@@ -1144,9 +1144,9 @@ void Engine::lm_head(int B, const float* x, int ldx) {
   }
 }
 
-void Engine::enqueue_decode_step(int B) {
+void Engine::enqueue_decode_step(int B, bool masked) {
   enqueue_decode_forward(B);
-  enqueue_sample(B);
+  enqueue_sample(B, masked);
 }
 
 void Engine::enqueue_decode_forward(int B) {
@@ -1236,9 +1236,8 @@ void Engine::set_sample_processors(const std::vector<float>& min_p, const std::v
 
 void Engine::take_processors(SampleArgs& s, int B) {
   if (!proc_rows_) return;
-  const int rows = proc_rows_, Bm = cfg_.max_batch;
-  proc_rows_ = 0;  // one shot, also when the launch does not happen
-  if (rows != B) throw std::runtime_error("sample processors staged for another batch size");
+  const int Bm = cfg_.max_batch;
+  proc_rows_ = 0;  // one shot (the caller's SampleStage checked the rows)
   const size_t wbytes = (size_t)Bm * 16 + (size_t)B * proc_stride_ * 4;
   const size_t nbytes = wbytes + (size_t)B * proc_bias_stride_ * 8;
   HIP_CHECK(hipMemcpyAsync(d_proc_, h_proc_, nbytes, hipMemcpyHostToDevice, stream_));
@@ -1273,9 +1272,8 @@ void Engine::set_logprobs(const std::vector<int>& top_n) {
 void Engine::take_logprobs(int B) {
   lp_last_.clear();
   if (!lp_rows_) return;
-  const int rows = lp_rows_, Bm = cfg_.max_batch;
-  lp_rows_ = 0;  // one shot, also when the launch does not happen
-  if (rows != B) throw std::runtime_error("logprobs staged for another batch size");
+  const int Bm = cfg_.max_batch;
+  lp_rows_ = 0;  // one shot (the caller's SampleStage checked the rows)
   const int* hn = (const int*)h_lp_;
   HIP_CHECK(hipMemcpyAsync(d_lp_topn_, hn, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
   LogprobArgs a;
@@ -1321,15 +1319,20 @@ SampleArgs Engine::sample_args(int B, bool masked) const {
   return s;
 }
 
-void Engine::enqueue_sample(int B, bool processors) {
-  SampleArgs s = sample_args(B, sample_mask_);
-  s.seed = sample_seed_;
-  s.seed_dev = d_seed_;
-  s.pos = d_pos_; s.seq_len = d_seqlen_;
-  s.history = d_history_; s.hist_stride = cfg_.max_ctx + 1;
-  s.advance = 1;
-  if (processors) take_processors(s, B);
+void Engine::enqueue_sample(int B, bool masked, SampleKind kind, bool staged) {
+  SampleArgs s = sample_args(B, masked);
+  // FIRST: no seed_dev, the key is the row seed and pos alone; AGAIN: pos was advanced by the step, so the RNG
+  // key differs from the first sample's
+  if (kind != SAMPLE_FIRST) s.seed_dev = d_seed_;
+  s.pos = kind == SAMPLE_FIRST ? d_fpos_ : d_pos_;
+  if (kind == SAMPLE_STEP) {
+    s.seq_len = d_seqlen_;
+    s.history = d_history_; s.hist_stride = cfg_.max_ctx + 1;
+    s.advance = 1;
+  }
+  if (staged) take_processors(s, B);
   launch_sample(s, stream_);
+  if (staged) take_logprobs(B);
 }
 
 bool Engine::gemm_prefill_ok(int T) const { return gm_ok_ && T >= gm_min_rows_; }
@@ -1741,52 +1744,27 @@ std::vector<int> Engine::decode(const std::vector<int>& slots, const std::vector
   if (!finalized_) throw std::runtime_error("engine not finalized");
   HIP_CHECK(hipSetDevice(cfg_.device));
   const int B = (int)slots.size();
-  const LogprobStage lp_stage(lp_rows_, B, "decode");  // (before the step changes any state)
-  if (!seeds.empty() && (int)seeds.size() != B) throw std::runtime_error("decode: seeds size mismatch");
-  if (B < 1 || B > cfg_.max_batch) throw std::runtime_error("decode: batch out of range");
-  if ((int)tokens.size() != B || (int)pos.size() != B) throw std::runtime_error("decode: size mismatch");
-  const ProcessorStage proc_stage(proc_rows_, B, "decode");  // (before the step changes any state)
-  for (int b = 0; b < B; ++b) {
-    if (pos[b] < 0 || pos[b] >= cfg_.max_ctx) throw std::runtime_error("decode: position out of range");
-    if (slots[b] < 0 || slots[b] >= cfg_.max_slots) throw std::runtime_error("decode: bad slot");
-    if (tokens[b] < 0 || tokens[b] >= cfg_.vocab_size) throw std::runtime_error("decode: token out of range");
-  }
+  const SampleStage stage(*this, B, "decode");  // (before the step changes any state)
+  check_step("decode", slots, tokens, pos, seeds, true);
+  const bool masked = !mask.empty();
+  if (masked && mask.size() != (size_t)B * ((cfg_.vocab_size + 7) / 8))
+    throw std::runtime_error("decode: mask size mismatch");
   row_slots_ = slots;
   row_pos_ = pos;
-  const size_t mbytes = (size_t)B * ((cfg_.vocab_size + 7) / 8);
-  sample_mask_ = !mask.empty();
-  if (sample_mask_ && mask.size() != mbytes) throw std::runtime_error("decode: mask size mismatch");
   // one pinned staging block -> one async copy; the device-resident seed lets one captured graph per
   // (B, masked) serve every request
-  write_step_params(h_par_, slots, tokens, pos, temperature, top_k, top_p, seed, seeds);
-  size_t nbytes = par_seeds_off_ + (size_t)cfg_.max_batch * 8;
-  if (sample_mask_) {
-    std::memcpy(h_par_ + par_mask_off_, mask.data(), mbytes);
-    nbytes = par_mask_off_ + mbytes;
-  }
-  HIP_CHECK(hipMemcpyAsync(d_par_, h_par_, nbytes, hipMemcpyHostToDevice, stream_));
+  upload_step_params(slots, tokens, pos, temperature, top_k, top_p, seed, seeds, mask);
   if (proc_rows_ || lp_rows_) {
     // staged logit processors / logprobs: the forward graph and an eager sampler (and logprob launch), as
     // the pipelined path runs a step -- the captured (B, masked) step graphs never see them
-    for (int b = 0; b < B; ++b) {
-      kv_prepare_write(row_slots_[b], row_pos_[b], std::min(row_pos_[b] + 1, cfg_.max_ctx));
-      row_pos_[b] = std::min(row_pos_[b] + 1, cfg_.max_ctx);
-    }
-    kv_sync(B);
+    advance_rows(B, 1);
     HIP_CHECK(hipGraphLaunch(forward_graph(B), stream_));
-    try {
-      enqueue_sample(B, true);
-      take_logprobs(B);
-    } catch (...) {
-      sample_mask_ = false;
-      throw;
-    }
+    enqueue_sample(B, masked, SAMPLE_STEP, true);
   } else {
-    decode_loop_run(B, 1, true);
+    decode_loop_body(B, 1, true, masked);
   }
   HIP_CHECK(hipMemcpyAsync(h_tok_out_, d_tokens_, B * 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
-  sample_mask_ = false;
   return std::vector<int>(h_tok_out_, h_tok_out_ + B);
 }
 
@@ -1796,54 +1774,36 @@ Engine::SpecResult Engine::spec_decode(int slot, const std::vector<int>& tokens,
   if (!finalized_) throw std::runtime_error("engine not finalized");
   HIP_CHECK(hipSetDevice(cfg_.device));
   const int R = (int)tokens.size();
-  const LogprobStage lp_stage(lp_rows_, R, "spec_decode");  // (before the step changes any state)
+  const SampleStage stage(*this, R, "spec_decode");  // (before the step changes any state)
   if (cfg_.tp_size > 1) throw std::runtime_error("spec_decode: not available on a tensor-parallel engine");
   if (pipe_sampled_) throw std::runtime_error("spec_decode: a pipelined step is in flight");
   if (R < 2 || R > std::min(cfg_.max_batch, SPEC_MAX_ROWS)) throw std::runtime_error("spec_decode: rows out of range");
   if (slot < 0 || slot >= cfg_.max_slots) throw std::runtime_error("spec_decode: bad slot");
   if (pos0 < 0 || pos0 + R > cfg_.max_ctx) throw std::runtime_error("spec_decode: positions out of range");
-  const ProcessorStage proc_stage(proc_rows_, R, "spec_decode");  // (before the step changes any state)
   for (int t : tokens)
     if (t < 0 || t >= cfg_.vocab_size) throw std::runtime_error("spec_decode: token out of range");
-  const size_t mbytes = (size_t)R * ((cfg_.vocab_size + 7) / 8);
-  if (!masks.empty() && masks.size() != mbytes) throw std::runtime_error("spec_decode: mask size mismatch");
-  sample_mask_ = !masks.empty();
+  if (!masks.empty() && masks.size() != (size_t)R * ((cfg_.vocab_size + 7) / 8))
+    throw std::runtime_error("spec_decode: mask size mismatch");
   // the rows of decode(): one slot, consecutive positions, the request's parameters and seed on every row
   row_slots_.assign(R, slot);
   row_pos_.resize(R);
   for (int i = 0; i < R; ++i) row_pos_[i] = pos0 + i;
-  par_buf_ ^= 1;  // (decode_submit's rule: the copy of a forward the scheduler queued and dropped may not have run yet)
-  char* hpar = h_par_ + (size_t)par_buf_ * par_bytes_;
-  write_step_params(hpar, row_slots_, tokens, row_pos_, std::vector<float>(R, temperature), std::vector<int>(R, top_k),
-                    std::vector<float>(R, top_p), seed, std::vector<uint64_t>(R, seed));
-  size_t nbytes = par_seeds_off_ + (size_t)cfg_.max_batch * 8;
-  if (sample_mask_) {
-    std::memcpy(hpar + par_mask_off_, masks.data(), mbytes);
-    nbytes = par_mask_off_ + mbytes;
-  }
-  HIP_CHECK(hipMemcpyAsync(d_par_, hpar, nbytes, hipMemcpyHostToDevice, stream_));
+  upload_step_params(row_slots_, tokens, row_pos_, std::vector<float>(R, temperature), std::vector<int>(R, top_k),
+                     std::vector<float>(R, top_p), seed, std::vector<uint64_t>(R, seed), masks);
   // the input tokens once more, apart from d_tokens_ (the sampler overwrites those)
   std::copy(tokens.begin(), tokens.end(), h_spec_);
   HIP_CHECK(hipMemcpyAsync(d_spec_, h_spec_, (size_t)R * 4, hipMemcpyHostToDevice, stream_));
-  for (int i = 0; i < R; ++i) kv_prepare_write(slot, pos0 + i, pos0 + i + 1);
-  kv_sync(R);
+  advance_rows(R, 1);  // (the host rows become the one row behind the accepted tokens below)
   HIP_CHECK(hipGraphLaunch(forward_graph(R), stream_));
+  enqueue_sample(R, !masks.empty(), SAMPLE_STEP, true);
+  SpecAcceptArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.in = d_spec_; a.out = d_tokens_; a.pos0 = pos0; a.R = R;
+  a.record = d_spec_ + SPEC_MAX_ROWS;
+  a.tokens = d_tokens_; a.pos = d_pos_; a.seq_len = d_seqlen_;
+  a.history = d_history_; a.hist_stride = cfg_.max_ctx + 1;
+  launch_spec_accept(a, stream_);
   int* h_rec = h_spec_ + SPEC_MAX_ROWS;
-  try {
-    enqueue_sample(R, true);
-    take_logprobs(R);
-    SpecAcceptArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.in = d_spec_; a.out = d_tokens_; a.pos0 = pos0; a.R = R;
-    a.record = d_spec_ + SPEC_MAX_ROWS;
-    a.tokens = d_tokens_; a.pos = d_pos_; a.seq_len = d_seqlen_;
-    a.history = d_history_; a.hist_stride = cfg_.max_ctx + 1;
-    launch_spec_accept(a, stream_);
-  } catch (...) {
-    sample_mask_ = false;
-    throw;
-  }
-  sample_mask_ = false;
   HIP_CHECK(hipMemcpyAsync(h_rec, d_spec_ + SPEC_MAX_ROWS, (size_t)SPEC_RECORD * 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
   SpecResult r;
@@ -1860,32 +1820,15 @@ std::vector<int> Engine::resample(int B, const std::vector<float>& temperature, 
   const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
   // re-run only the sampler on the logits of the last step (grammar fast path: the unmasked
   // sample was rejected on the host)
-  const LogprobStage lp_stage(lp_rows_, B, "resample");  // (before the sampler is enqueued)
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  const SampleStage stage(*this, B, "resample");  // (before the sampler is enqueued)
+  if (B < 1 || B > cfg_.max_batch) throw std::runtime_error("resample: batch out of range");
   HIP_CHECK(hipSetDevice(cfg_.device));
-  std::vector<float> temps(B, 0.f);
-  std::vector<int> tks(B, 0);
-  for (int b = 0; b < B && b < (int)temperature.size(); ++b) temps[b] = temperature[b];
-  for (int b = 0; b < B && b < (int)top_k.size(); ++b) tks[b] = top_k[b];
-  HIP_CHECK(hipMemcpyAsync(d_temp_, temps.data(), B * 4, hipMemcpyHostToDevice, stream_));
-  HIP_CHECK(hipMemcpyAsync(d_topk_, tks.data(), B * 4, hipMemcpyHostToDevice, stream_));
-  std::vector<float> tps(B, 1.f);
-  for (int b = 0; b < B && b < (int)top_p.size(); ++b) tps[b] = top_p[b];
-  HIP_CHECK(hipMemcpyAsync(d_topp_, tps.data(), B * 4, hipMemcpyHostToDevice, stream_));
-  HIP_CHECK(hipMemcpyAsync(d_seed_, &seed, 8, hipMemcpyHostToDevice, stream_));
-  std::vector<uint64_t> hs(B);
-  fill_row_seeds(hs.data(), B, seed, {});
-  HIP_CHECK(hipMemcpyAsync(d_seeds_, hs.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream_));
   const size_t mbytes = (size_t)B * ((cfg_.vocab_size + 7) / 8);
-  if (!mask.empty()) {
-    if (mask.size() != mbytes) throw std::runtime_error("resample: mask size mismatch");
-    HIP_CHECK(hipMemcpyAsync(d_mask_, mask.data(), mbytes, hipMemcpyHostToDevice, stream_));
-  }
-  SampleArgs s = sample_args(B, !mask.empty());
-  s.seed_dev = d_seed_; s.pos = d_pos_; s.advance = 0;
-  take_processors(s, B);
-  // pos was advanced by the step: RNG key uses pos[b] (a different stream than the first sample)
-  launch_sample(s, stream_);
-  take_logprobs(B);
+  if (!mask.empty() && mask.size() != mbytes) throw std::runtime_error("resample: mask size mismatch");
+  upload_sample_params(B, temperature, top_k, top_p, seed, {}, true);
+  if (!mask.empty()) HIP_CHECK(hipMemcpyAsync(d_mask_, mask.data(), mbytes, hipMemcpyHostToDevice, stream_));
+  enqueue_sample(B, !mask.empty(), SAMPLE_AGAIN, true);
   std::vector<int> out(B);
   HIP_CHECK(hipMemcpyAsync(out.data(), d_tokens_, B * 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
@@ -1902,22 +1845,15 @@ int Engine::sample_first(int pos, float temperature, int top_k, float top_p, uin
                          const std::vector<uint8_t>& mask) {
   const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
   if (!finalized_) throw std::runtime_error("engine not finalized");
-  const LogprobStage lp_stage(lp_rows_, 1, "sample_first");  // (before the sampler is enqueued)
+  const SampleStage stage(*this, 1, "sample_first");  // (before the sampler is enqueued)
   HIP_CHECK(hipSetDevice(cfg_.device));
   const size_t mbytes = (size_t)((cfg_.vocab_size + 7) / 8);
   if (!mask.empty() && mask.size() != mbytes) throw std::runtime_error("sample_first: mask size mismatch");
-  // row 0 of the parameter block: the next decode() re-uploads every row it uses
-  HIP_CHECK(hipMemcpyAsync(d_temp_, &temperature, 4, hipMemcpyHostToDevice, stream_));
-  HIP_CHECK(hipMemcpyAsync(d_topk_, &top_k, 4, hipMemcpyHostToDevice, stream_));
-  HIP_CHECK(hipMemcpyAsync(d_topp_, &top_p, 4, hipMemcpyHostToDevice, stream_));
-  HIP_CHECK(hipMemcpyAsync(d_seeds_, &seed, 8, hipMemcpyHostToDevice, stream_));
+  // row 0 of the parameter block (its row seed: the request's own): the next decode() re-uploads every row it uses
+  upload_sample_params(1, {temperature}, {top_k}, {top_p}, seed, {seed}, false);
   HIP_CHECK(hipMemcpyAsync(d_fpos_, &pos, 4, hipMemcpyHostToDevice, stream_));
   if (!mask.empty()) HIP_CHECK(hipMemcpyAsync(d_mask_, mask.data(), mbytes, hipMemcpyHostToDevice, stream_));
-  SampleArgs s = sample_args(1, !mask.empty());
-  s.pos = d_fpos_; s.advance = 0;  // (no seed_dev: the key is the row seed and pos alone)
-  take_processors(s, 1);
-  launch_sample(s, stream_);
-  take_logprobs(1);
+  enqueue_sample(1, !mask.empty(), SAMPLE_FIRST, true);
   int out = 0;
   HIP_CHECK(hipMemcpyAsync(&out, d_tokens_, 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
@@ -1956,29 +1892,34 @@ void Engine::decode_loop_prepare(const std::vector<int>& slots, const std::vecto
   fill_row_seeds(hs.data(), B, 0, {});
   HIP_CHECK(hipMemcpyAsync(d_seeds_, hs.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
-  sample_seed_ = 0;
-  sample_mask_ = false;
 }
 
-void Engine::decode_loop_run(int B, int n_steps, bool use_graph) {
+void Engine::decode_loop_run(int B, int n_steps, bool use_graph) { decode_loop_body(B, n_steps, use_graph, false); }
+
+void Engine::decode_loop_body(int B, int n_steps, bool use_graph, bool masked) {
   const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
   TraceRange tr(use_graph ? "aios.decode_graph_replay" : "aios.decode_eager");
   HIP_CHECK(hipSetDevice(cfg_.device));
   if ((int)row_slots_.size() < B) throw std::runtime_error("decode_loop_run: rows not prepared");
-  lp_last_.clear();  // (captured steps never carry a logprob launch: a staging is dropped, not kept for later)
-  lp_rows_ = 0;
-  // map (and un-share) the blocks the n steps will write, before any of them is enqueued
-  for (int b = 0; b < B; ++b) {
-    kv_prepare_write(row_slots_[b], row_pos_[b], std::min(row_pos_[b] + n_steps, cfg_.max_ctx));
-    row_pos_[b] = std::min(row_pos_[b] + n_steps, cfg_.max_ctx);
-  }
-  kv_sync(B);
+  // (these steps never carry staged processors or a logprob launch: a staging is dropped, not kept for later)
+  lp_last_.clear();
+  proc_rows_ = lp_rows_ = 0;
+  advance_rows(B, n_steps);
   if (!use_graph) {
-    for (int i = 0; i < n_steps; ++i) enqueue_decode_step(B);
+    for (int i = 0; i < n_steps; ++i) enqueue_decode_step(B, masked);
     return;
   }
-  hipGraphExec_t ge = step_graph(B);
+  hipGraphExec_t ge = step_graph(B, masked);
   for (int i = 0; i < n_steps; ++i) HIP_CHECK(hipGraphLaunch(ge, stream_));
+}
+
+void Engine::advance_rows(int B, int n) {
+  for (int b = 0; b < B; ++b) {
+    const int to = std::min(row_pos_[b] + n, cfg_.max_ctx);
+    kv_prepare_write(row_slots_[b], row_pos_[b], to);
+    row_pos_[b] = to;
+  }
+  kv_sync(B);
 }
 
 hipGraphExec_t Engine::graph_for(int key, const std::function<void()>& enqueue) {
@@ -2001,10 +1942,10 @@ hipGraphExec_t Engine::graph_for(int key, const std::function<void()>& enqueue) 
   return it->second;
 }
 
-// the captured decode step for (B, sample_mask_): captured once, replayed for every request --
+// the captured decode step for (B, masked): captured once, replayed for every request --
 // the kernels read tokens / positions / slots / sampling parameters from device arrays
-hipGraphExec_t Engine::step_graph(int B) {
-  return graph_for(B * 4 + (sample_mask_ ? 1 : 0), [&] { enqueue_decode_step(B); });
+hipGraphExec_t Engine::step_graph(int B, bool masked) {
+  return graph_for(B * 4 + (masked ? 1 : 0), [&] { enqueue_decode_step(B, masked); });
 }
 
 // the forward of a decode step without its sampler (the pipelined decode's graph)
@@ -2017,19 +1958,76 @@ void Engine::write_step_params(char* hpar, const std::vector<int>& slots, const 
                                const std::vector<int>& top_k, const std::vector<float>& top_p, uint64_t seed,
                                const std::vector<uint64_t>& seeds) {
   const int B = (int)slots.size();
-  *(uint64_t*)hpar = seed;
   int *hs = (int*)(hpar + par_off(PAR_SLOT)), *ht = (int*)(hpar + par_off(PAR_TOKEN));
   int *hp = (int*)(hpar + par_off(PAR_POS)), *hl = (int*)(hpar + par_off(PAR_SEQLEN));
-  int* hk = (int*)(hpar + par_off(PAR_TOPK));
-  float *hT = (float*)(hpar + par_off(PAR_TEMP)), *hP = (float*)(hpar + par_off(PAR_TOPP));
   for (int b = 0; b < B; ++b) {
     hs[b] = slots[b]; hp[b] = pos[b]; hl[b] = pos[b] + 1;
     if (!tokens.empty()) ht[b] = tokens[b];
+  }
+  write_sample_params(hpar, B, temperature, top_k, top_p, seed, seeds);
+}
+
+void Engine::write_sample_params(char* hpar, int B, const std::vector<float>& temperature, const std::vector<int>& top_k,
+                                 const std::vector<float>& top_p, uint64_t seed, const std::vector<uint64_t>& seeds) {
+  *(uint64_t*)hpar = seed;
+  int* hk = (int*)(hpar + par_off(PAR_TOPK));
+  float *hT = (float*)(hpar + par_off(PAR_TEMP)), *hP = (float*)(hpar + par_off(PAR_TOPP));
+  for (int b = 0; b < B; ++b) {
     hk[b] = b < (int)top_k.size() ? top_k[b] : 0;
     hT[b] = b < (int)temperature.size() ? temperature[b] : 0.f;
     hP[b] = b < (int)top_p.size() ? top_p[b] : 1.f;
   }
   fill_row_seeds((uint64_t*)(hpar + par_seeds_off_), B, seed, seeds);
+}
+
+void Engine::par_copy(const char* hpar, size_t from, size_t to) {
+  HIP_CHECK(hipMemcpyAsync(d_par_ + from, hpar + from, to - from, hipMemcpyHostToDevice, stream_));
+}
+
+void Engine::upload_step_params(const std::vector<int>& slots, const std::vector<int>& tokens,
+                                const std::vector<int>& pos, const std::vector<float>& temperature,
+                                const std::vector<int>& top_k, const std::vector<float>& top_p, uint64_t seed,
+                                const std::vector<uint64_t>& seeds, const std::vector<uint8_t>& mask) {
+  // the other half: the copy of the previous upload may not have run yet (a pipelined step's, or that of a
+  // forward the scheduler queued and dropped)
+  char* hpar = next_par();
+  write_step_params(hpar, slots, tokens, pos, temperature, top_k, top_p, seed, seeds);
+  size_t from = 0, end = par_seeds_off_ + (size_t)cfg_.max_batch * 8;
+  if (!mask.empty()) {
+    std::memcpy(hpar + par_mask_off_, mask.data(), mask.size());
+    end = par_mask_off_ + mask.size();
+  }
+  if (tokens.empty()) {  // every row array but the tokens the previous sampler left on the device
+    par_copy(hpar, 0, par_off(PAR_TOKEN));
+    from = par_off(PAR_TOKEN + 1);
+  }
+  par_copy(hpar, from, end);
+}
+
+void Engine::upload_sample_params(int B, const std::vector<float>& temperature, const std::vector<int>& top_k,
+                                  const std::vector<float>& top_p, uint64_t seed, const std::vector<uint64_t>& seeds,
+                                  bool dev_seed) {
+  char* hpar = next_par();
+  write_sample_params(hpar, B, temperature, top_k, top_p, seed, seeds);
+  if (dev_seed) par_copy(hpar, 0, 8);
+  par_copy(hpar, par_off(PAR_TOPK), par_off(PAR_TOPP) + (size_t)B * 4);  // (rows past B of top_k / temperature too)
+  par_copy(hpar, par_seeds_off_, par_seeds_off_ + (size_t)B * 8);
+}
+
+void Engine::check_step(const std::string& who, const std::vector<int>& slots, const std::vector<int>& tokens,
+                        const std::vector<int>& pos, const std::vector<uint64_t>& seeds, bool need_tokens) const {
+  const int B = (int)slots.size();
+  const bool host_tokens = need_tokens || !tokens.empty();
+  if (B < 1 || B > cfg_.max_batch) throw std::runtime_error(who + ": batch out of range");
+  if ((int)pos.size() != B || (host_tokens && (int)tokens.size() != B))
+    throw std::runtime_error(who + ": size mismatch");
+  if (!seeds.empty() && (int)seeds.size() != B) throw std::runtime_error(who + ": seeds size mismatch");
+  for (int b = 0; b < B; ++b) {
+    if (pos[b] < 0 || pos[b] >= cfg_.max_ctx) throw std::runtime_error(who + ": position out of range");
+    if (slots[b] < 0 || slots[b] >= cfg_.max_slots) throw std::runtime_error(who + ": bad slot");
+    if (host_tokens && (tokens[b] < 0 || tokens[b] >= cfg_.vocab_size))
+      throw std::runtime_error(who + ": token out of range");
+  }
 }
 
 void Engine::decode_submit(const std::vector<int>& slots, const std::vector<int>& tokens, const std::vector<int>& pos,
@@ -2039,33 +2037,11 @@ void Engine::decode_submit(const std::vector<int>& slots, const std::vector<int>
   if (!finalized_) throw std::runtime_error("engine not finalized");
   HIP_CHECK(hipSetDevice(cfg_.device));
   const int B = (int)slots.size();
-  if (B < 1 || B > cfg_.max_batch) throw std::runtime_error("decode_submit: batch out of range");
-  if ((int)pos.size() != B || (!tokens.empty() && (int)tokens.size() != B) || (!seeds.empty() && (int)seeds.size() != B))
-    throw std::runtime_error("decode_submit: size mismatch");
-  for (int b = 0; b < B; ++b) {
-    if (pos[b] < 0 || pos[b] >= cfg_.max_ctx) throw std::runtime_error("decode_submit: position out of range");
-    if (slots[b] < 0 || slots[b] >= cfg_.max_slots) throw std::runtime_error("decode_submit: bad slot");
-    if (!tokens.empty() && (tokens[b] < 0 || tokens[b] >= cfg_.vocab_size))
-      throw std::runtime_error("decode_submit: token out of range");
-  }
-  par_buf_ ^= 1;  // the other half: the previous submit's copy may not have run yet
-  char* hpar = h_par_ + (size_t)par_buf_ * par_bytes_;
-  write_step_params(hpar, slots, tokens, pos, temperature, top_k, top_p, seed, seeds);
-  const size_t tok_off = par_off(PAR_TOKEN), end = par_seeds_off_ + (size_t)cfg_.max_batch * 8;
-  if (tokens.empty()) {  // every row array but the tokens the previous sampler left on the device
-    const size_t after = par_off(PAR_TOKEN + 1);
-    HIP_CHECK(hipMemcpyAsync(d_par_, hpar, tok_off, hipMemcpyHostToDevice, stream_));
-    HIP_CHECK(hipMemcpyAsync(d_par_ + after, hpar + after, end - after, hipMemcpyHostToDevice, stream_));
-  } else {
-    HIP_CHECK(hipMemcpyAsync(d_par_, hpar, end, hipMemcpyHostToDevice, stream_));
-  }
+  check_step("decode_submit", slots, tokens, pos, seeds, false);
+  upload_step_params(slots, tokens, pos, temperature, top_k, top_p, seed, seeds);  // (no mask: decode_sample's)
   row_slots_ = slots;
   row_pos_ = pos;
-  for (int b = 0; b < B; ++b) {
-    kv_prepare_write(slots[b], pos[b], pos[b] + 1);
-    row_pos_[b] = pos[b] + 1;
-  }
-  kv_sync(B);
+  advance_rows(B, 1);
   HIP_CHECK(hipGraphLaunch(forward_graph(B), stream_));
   pipe_B_ = B;
 }
@@ -2074,7 +2050,7 @@ void Engine::decode_sample(const std::vector<uint8_t>& mask) {
   const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
   const int B = pipe_B_;
   if (B < 1) throw std::runtime_error("decode_sample: no submitted step");
-  const LogprobStage lp_stage(lp_rows_, B, "decode_sample");  // (before the sampler is enqueued)
+  const SampleStage stage(*this, B, "decode_sample");  // (before the sampler is enqueued)
   HIP_CHECK(hipSetDevice(cfg_.device));
   const size_t mbytes = (size_t)B * ((cfg_.vocab_size + 7) / 8);
   if (!mask.empty()) {
@@ -2084,15 +2060,7 @@ void Engine::decode_sample(const std::vector<uint8_t>& mask) {
     std::memcpy(h_mask_, mask.data(), mbytes);
     HIP_CHECK(hipMemcpyAsync(d_mask_, h_mask_, mbytes, hipMemcpyHostToDevice, stream_));
   }
-  sample_mask_ = !mask.empty();
-  try {
-    enqueue_sample(B, true);
-    take_logprobs(B);
-  } catch (...) {
-    sample_mask_ = false;
-    throw;
-  }
-  sample_mask_ = false;
+  enqueue_sample(B, !mask.empty(), SAMPLE_STEP, true);
   HIP_CHECK(hipMemcpyAsync(h_tok_out_, d_tokens_, B * 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipEventRecord(pipe_ev_, stream_));
   pipe_sampled_ = true;
@@ -2113,14 +2081,11 @@ int Engine::capture_graphs(int max_b) {
   const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
   if (!finalized_) throw std::runtime_error("engine not finalized");
   HIP_CHECK(hipSetDevice(cfg_.device));
-  const bool saved = sample_mask_;
-  for (int B = 1; B <= std::min(max_b, cfg_.max_batch); ++B)
-    for (int m = 0; m < 2; ++m) {
-      sample_mask_ = m != 0;
-      step_graph(B);
-      if (m == 0) forward_graph(B);  // (the pipelined decode's forward)
-    }
-  sample_mask_ = saved;
+  for (int B = 1; B <= std::min(max_b, cfg_.max_batch); ++B) {
+    step_graph(B, false);
+    forward_graph(B);  // (the pipelined decode's forward)
+    step_graph(B, true);
+  }
   return (int)graphs_.size();
 }
 

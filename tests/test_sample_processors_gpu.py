@@ -252,3 +252,98 @@ def test_engine_processors_validation(small_engine):
         eng.set_sample_processors([0.0], [1.0], [0.0], [0.0], [[cfg.vocab_size]])
     with pytest.raises(RuntimeError, match="batch out of range"):
         eng.set_sample_processors([0.0] * 3, [1.0] * 3, [0.0] * 3, [0.0] * 3, [[1]] * 3)
+
+
+def ban(V, tok):
+    """a one-row grammar mask that allows every token but tok"""
+    bits = np.ones(V, np.uint8)
+    bits[tok] = 0
+    return np.packbits(bits, bitorder="little").tobytes()
+
+
+def greedy_step(eng):
+    """prefill slot 0, then the decode step (token t0 at position 4) the staging tests repeat: its token t0,
+    its logits and their argmax"""
+    t0 = int(np.argmax(np.asarray(eng.prefill(0, [1, 33, 44, 55], 0, True))))
+    tok = eng.decode([0], [t0], [4], [0.0], [0], 0, b"")[0]
+    lg = np.asarray(eng.last_logits(1)).reshape(-1)
+    assert tok == int(np.argmax(lg))
+    return t0, lg, tok
+
+
+@pytest.mark.parametrize("with_logprobs", [False, True])
+def test_throwing_call_drops_processors(small_engine, with_logprobs):
+    """a decode that is refused (position out of range) drops the staged processors, and the staged logprobs
+    beside them: the next valid decode of the row is the plain argmax and reports no logprobs"""
+    eng, cfg = small_engine
+    t0, lg, tok = greedy_step(eng)
+    assert int(np.argmax(host.apply_penalties(lg, [tok], 1.0, 1e4, 0.0))) != tok   # (the penalty would move it)
+    eng.set_sample_processors([0.0], [1.0], [1e4], [0.0], [[tok]])
+    if with_logprobs:
+        eng.set_logprobs([5])
+    with pytest.raises(RuntimeError, match="position out of range"):
+        eng.decode([0], [t0], [10 ** 6], [0.0], [0], 0, b"")
+    assert eng.decode([0], [t0], [4], [0.0], [0], 0, b"")[0] == tok
+    if with_logprobs:
+        assert len(eng.last_logprobs()) == 0
+
+
+def test_decode_loop_run_drops_processors(small_engine):
+    """the graph-replayed loop carries no processors: staged ones are dropped there, not kept for the resample"""
+    eng, cfg = small_engine
+    t0, lg, tok = greedy_step(eng)
+    assert int(np.argmax(host.apply_penalties(lg, [tok], 1.0, 1e4, 0.0))) != tok
+    eng.set_sample_processors([0.0], [1.0], [1e4], [0.0], [[tok]])
+    eng.decode_loop_prepare([0], [t0], [4])
+    eng.decode_loop_run(1, 1, True)
+    eng.synchronize()
+    assert eng.resample(1, [0.0], [0], 0, b"")[0] == tok
+
+
+@pytest.mark.parametrize("masked_first", [True, False])
+def test_mask_argument_carries_no_state(small_engine, masked_first):
+    """a masked and an unmasked decode of the same row, token and position on one engine, in either order,
+    with and without capture_graphs between them: the mask bans the argmax in the one and nothing in the other"""
+    eng, cfg = small_engine
+    t0, lg, best = greedy_step(eng)
+    rest = lg.copy()
+    rest[best] = -np.inf
+    calls = [(ban(cfg.vocab_size, best), int(np.argmax(rest))), (b"", best)]
+    first, second = calls if masked_first else calls[::-1]
+    for capture in (False, True):
+        assert eng.decode([0], [t0], [4], [0.0], [0], 0, first[0])[0] == first[1]
+        if capture:   # every graph of max_batch = 2: the unmasked and the masked step and the forward, per batch size
+            assert eng.capture_graphs(2) == 6
+        assert eng.decode([0], [t0], [4], [0.0], [0], 0, second[0])[0] == second[1]
+
+
+def test_sampler_only_calls_leave_the_step_rows_alone(small_engine):
+    """resample / sample_first between two pipelined steps upload sampling parameters only: the next
+    decode_submit(tokens = {}) continues from the slots, tokens, positions and lengths on the device, and gives
+    what the same steps give without the call in between"""
+    eng, cfg = small_engine
+    V, B = cfg.vocab_size, 2
+    prompts = [[1, 30, 40, 50, 60, 70, 80], [1, 31, 41, 51, 61]]
+
+    def run(between):
+        first = [int(np.argmax(np.asarray(eng.prefill(s, p, 0, True)))) for s, p in enumerate(prompts)]
+        pos = [len(p) for p in prompts]
+        eng.decode_submit([0, 1], first, pos, [0.0] * B, [0] * B, 0)
+        eng.decode_sample(b"")
+        out1 = [int(t) for t in eng.decode_collect()]
+        if between == "resample":
+            assert [int(t) for t in eng.resample(2, [0.0] * B, [0] * B, 0, b"")] == out1
+        elif between == "sample_first":   # (row 0 of the step's logits: the same greedy token)
+            assert eng.sample_first(pos[0], 0.0, 0, 1.0, 1, b"") == out1[0]
+        eng.decode_submit([0, 1], [], [p + 1 for p in pos], [0.0] * B, [0] * B, 0)
+        eng.decode_sample(b"")
+        out2 = [int(t) for t in eng.decode_collect()]
+        lg = np.asarray(eng.last_logits(B)).reshape(B, V)
+        assert out2 == [int(np.argmax(lg[b])) for b in range(B)]
+        return out1, out2, lg
+
+    want = run(None)
+    for between in ("resample", "sample_first"):
+        got = run(between)
+        assert got[:2] == want[:2], between
+        assert [int(np.argmax(r)) for r in got[2]] == [int(np.argmax(r)) for r in want[2]], between
