@@ -378,6 +378,29 @@ PYBIND11_MODULE(_engine, m) {
       .def("copy_slot", &Engine::copy_slot, py::call_guard<py::gil_scoped_release>())
       .def("release_slot", &Engine::release_slot)
       .def("block_table", &Engine::block_table)
+      .def("kv_read",
+           [](const Engine& e, int slot, int n_tokens) {
+             // raw cache bytes of a slot's first n_tokens positions: [layer][K, V][kv_head][token][head_dim]
+             std::vector<uint8_t> v;
+             {
+               py::gil_scoped_release nogil;
+               v = e.kv_read(slot, n_tokens);
+             }
+             return py::bytes((const char*)v.data(), v.size());
+           },
+           py::arg("slot"), py::arg("n_tokens"))
+      .def("kv_read_block",
+           [](const Engine& e, int block) {
+             // one physical block of every layer: [layer][K, V][kv_head][KV_BLOCK][head_dim]
+             std::vector<uint8_t> v;
+             {
+               py::gil_scoped_release nogil;
+               v = e.kv_read_block(block);
+             }
+             return py::bytes((const char*)v.data(), v.size());
+           },
+           py::arg("block"))
+      .def("kv_device_tables", &Engine::kv_device_tables, py::arg("B"), py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("kv_blocks_free", &Engine::kv_blocks_free)
       .def_property_readonly("kv_blocks_total", &Engine::kv_blocks_total)
       .def_property_readonly("norm_fused_parts", &Engine::norm_fused_parts)

@@ -294,6 +294,16 @@ class Engine {
   int kv_blocks_total() const { return kv_nblocks_; }
   int norm_fused_parts() const { return nrm_parts_; }  // 0: batched-decode RMSNorm not split into the GEMMs
   std::vector<int> block_table(int slot) const;
+  // read-only views of the cache for tests (host copies after a stream synchronise; raw bf16 / fp8 bytes):
+  // kv_read: positions [0, n_tokens) of a slot gathered through its host table, [layer][K, V][kv_head][token]
+  // [head_dim] (an unmapped block reads as the null block); kv_read_block: one physical block, [layer][K, V]
+  // [kv_head][KV_BLOCK][head_dim] (block == kv_blocks_total: the null block)
+  std::vector<uint8_t> kv_read(int slot, int n_tokens) const;
+  std::vector<uint8_t> kv_read_block(int block) const;
+  // the tables as the kernels see them, read back from the device: the slot table [max_slots][max_ctx / KV_BLOCK],
+  // then the first B rows of the decode batch's row table (unmapped entries: kv_blocks_total).  They are what
+  // kv_sync last uploaded: release_slot alone uploads nothing
+  std::vector<int> kv_device_tables(int B) const;
 
   // raw device pointers for tests / custom kernels
   uintptr_t kv_cache_k() const { return (uintptr_t)k_cache_; }

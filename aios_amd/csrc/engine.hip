@@ -2286,4 +2286,60 @@ std::vector<int> Engine::block_table(int slot) const {
   return std::vector<int>(bt_.begin() + (size_t)slot * kv_maxb_, bt_.begin() + (size_t)(slot + 1) * kv_maxb_);
 }
 
+std::vector<uint8_t> Engine::kv_read(int slot, int n_tokens) const {
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  if (slot < 0 || slot >= cfg_.max_slots) throw std::runtime_error("kv_read: bad slot");
+  if (n_tokens < 0 || n_tokens > cfg_.max_ctx) throw std::runtime_error("kv_read: token count out of range");
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  const size_t row = (size_t)cfg_.head_dim * kv_es_;                 // one position of one head, bytes
+  const size_t blk = (size_t)cfg_.n_kv_heads * KV_BLOCK * row;       // one block of one pool, bytes
+  std::vector<uint8_t> out((size_t)cfg_.n_layers * 2 * cfg_.n_kv_heads * n_tokens * row);
+  uint8_t* o = out.data();
+  for (int l = 0; l < cfg_.n_layers; ++l)
+    for (bf16_t* base : {k_cache_, v_cache_}) {
+      const char* lb = (const char*)kv_layer(base, l);
+      for (int h = 0; h < cfg_.n_kv_heads; ++h)
+        for (int t0 = 0; t0 < n_tokens; t0 += KV_BLOCK) {
+          const int b = bt_[(size_t)slot * kv_maxb_ + t0 / KV_BLOCK];
+          const size_t n = (size_t)std::min(KV_BLOCK, n_tokens - t0) * row;
+          const char* src = lb + (size_t)(b < 0 ? kv_nblocks_ : b) * blk + (size_t)h * KV_BLOCK * row;
+          HIP_CHECK(hipMemcpyAsync(o, src, n, hipMemcpyDeviceToHost, stream_));
+          o += n;
+        }
+    }
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  return out;
+}
+
+std::vector<int> Engine::kv_device_tables(int B) const {
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  if (B < 0 || B > cfg_.max_batch) throw std::runtime_error("kv_device_tables: rows out of range");
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  const size_t ns = bt_.size(), nr = (size_t)B * kv_maxb_;
+  std::vector<int> out(ns + nr);
+  HIP_CHECK(hipMemcpyAsync(out.data(), d_bt_, ns * 4, hipMemcpyDeviceToHost, stream_));
+  if (nr) HIP_CHECK(hipMemcpyAsync(out.data() + ns, d_row_bt_, nr * 4, hipMemcpyDeviceToHost, stream_));
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  return out;
+}
+
+std::vector<uint8_t> Engine::kv_read_block(int block) const {
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  if (block < 0 || block > kv_nblocks_) throw std::runtime_error("kv_read_block: bad block");
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  const size_t blk = (size_t)cfg_.n_kv_heads * KV_BLOCK * cfg_.head_dim * kv_es_;
+  std::vector<uint8_t> out((size_t)cfg_.n_layers * 2 * blk);
+  uint8_t* o = out.data();
+  for (int l = 0; l < cfg_.n_layers; ++l)
+    for (bf16_t* base : {k_cache_, v_cache_}) {
+      HIP_CHECK(hipMemcpyAsync(o, (const char*)kv_layer(base, l) + (size_t)block * blk, blk, hipMemcpyDeviceToHost, stream_));
+      o += blk;
+    }
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  return out;
+}
+
 }  // namespace aios
