@@ -999,15 +999,6 @@ PYBIND11_MODULE(_engine, m) {
         return py::make_tuple(bm, bn, sp);
       },
       py::arg("segs"), py::arg("M"), py::arg("epi"), py::arg("ksplit") = 0);
-  m.def(
-      "gemm_pf_probe",
-      [](uintptr_t A, int lda, PyQMatrix* w, int M, uintptr_t C, int probe, uintptr_t st) {
-        GemmQArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.A = (const bf16_t*)A; a.lda = lda; a.nseg = 1; a.seg[0] = w->w; a.M = M; a.N = w->w.rows;
-        a.K = w->w.cols; a.C = (float*)C; a.ldc = a.N; a.epi = GEPI_STORE;
-        return gemm_pf_probe(a, probe, S(st));
-      });
   m.attr("GEPI_STORE") = (int)GEPI_STORE;
   m.attr("GEPI_ACCUM") = (int)GEPI_ACCUM;
   m.attr("GEPI_SWIGLU_BF16") = (int)GEPI_SWIGLU_BF16;

@@ -1,23 +1,29 @@
 // Prefill GEMM on the CDNA4 matrix cores, dequantising the packed weights ONCE per workgroup tile:
-//   C[M][N] (epilogue) = A[M][K] (bf16 activations) x W[N][K]^T (repacked Q4_K / Q6_K planes, or bf16)
-// SURVEY.md §2.7 K3 prefill column -- the work llama.cpp's mul_mat_q does inside the reference's
-// llama-server child (/root/reference/runtime/src/model_manager.rs:187-204) -- without any resident
-// dequantised copy of a weight and without a vendor GEMM (round-4 verdict item 1).
+//   C[M][N] (epilogue) = A[M][K] (bf16 activations) x W[N][K]^T (the GEMV engines' quantised planes, or bf16)
+// -- the work llama.cpp's mul_mat_q does -- without any resident dequantised copy of a weight and
+// without a vendor GEMM.
 //
-// Geometry (BM x BN tile, NW = BN / 32 waves): every wave owns ALL BM rows and 32 columns, i.e.
-// (BM / 16) x 2 accumulators of v_mfma_f32_16x16x32_bf16.  A wave therefore dequantises exactly
-// its own 32 columns' weights (each weight byte decoded once per workgroup, straight into MFMA B
-// fragments in registers -- no bf16 LDS image of the weights, no LDS write pass) while the
-// activation tile is shared by all waves through LDS.  Per 64-deep K-step a lane decodes 32
-// weights (one 8-byte code group of each of its two columns) against 2 x BM/16 MFMAs.
+// Common to the three bodies.  A workgroup owns a BM x BN tile (BM = 256 / 128 / 64); each wave owns
+// ALL BM rows and 32 columns, dequantises exactly its own columns' weights (each weight byte decoded
+// once per workgroup, straight into MFMA B fragments in registers -- no bf16 LDS image of the
+// weights, no LDS write pass) and shares the activation tile with the other waves through LDS (BM
+// rows x 128 B per 64-deep K-step, 16-B units XOR-swizzled by row so a ds_read_b128 lane group hits
+// distinct banks).  Everything is staged by global_load_lds (LDS-DMA: no VGPR staging, no ds_write)
+// in compile-time pieces, a wave fetching its own columns, so each wave waits with one counted
+// s_waitcnt vmcnt immediate -- the only vector-memory operations inside the loops are these DMAs, so
+// the counts are exact.  One raw s_barrier per K-step (in-flight LDS-DMA survives it), placed between
+// the two halves of the step's last MFMA phase; the next step's B fragments are decoded inside this
+// step's phases; the loops are branch-free.
 //
-// Staging: one LDS slot per K-step holds the A tile (BM rows x 128 B, 16-B units XOR-swizzled by
-// row so a ds_read_b128 lane group of 16 rows hits 16 distinct bank slots) and the tile's raw
-// weight bytes of that K-step (codes + per-format metadata), all moved by global_load_lds
-// (LDS-DMA: no VGPR staging, no ds_write).  NS slots, NS - 1 K-steps in flight, one raw s_barrier
-// per K-step (in-flight LDS-DMA survives it), counted s_waitcnt vmcnt -- the only vector-memory
-// operations inside the loop are these DMAs, so the counts are exact (CDNA guide §5 "Pipelining
-// across barriers", "Three .s-level traps").
+// The bodies and the launches they serve (PfTile, pf_launch below):
+//   pf4_body   128-column tiles of every format: 4 waves (one per SIMD), v_mfma_f32_32x32x16_bf16,
+//              a ring of per-K-step slots (Pf4Layout / Pf4Dma).
+//   pf8_body   256-column tiles of bf16 and of the Q5_K / Q4_0 / Q8_0 stacks (their Q6_K segments
+//              too): 8 waves (two per SIMD), v_mfma_f32_16x16x32_bf16, the same slot ring.
+//   pf8c_body  256-column tiles of the K-quant stacks (Q4_K, Q6_K, their mix): pf8 with the weight
+//              planes staged coalesced per half block / block (PfcLayout / PfcDma).
+// Each runs as a plain launch (grid = tiles x K slices), with the tail split (256-row tiles) or as
+// stream-K; one kernel per mode, pf_run_tile picking the body and the segment's format.
 //
 // Weight k order: chunk h (16 B) of a 64-weight Q4_K group holds weights 16h + i (low nibble of byte
 // i) and 32 + 16h + i (high nibble).  Lane quarter q of the 16x16x32 B fragment reads bytes
@@ -60,25 +66,23 @@ __device__ __forceinline__ void pf_qkv_out(const GemmQArgs& a, int m, int n, flo
   }
 }
 
-
-// slot layout for one K-step: A, then the weight planes of BN columns
-template <int QT, int BM, int BN>
-struct PfLayout {
-  static constexpr bool Q6 = QT == QT_Q6_K, BF = QT == QT_BF16;
-  static constexpr int A_BYTES = BM * 128;
-  static constexpr int CODE = BF ? BN * 128 : BN * 32;        // bf16 rows (swizzled as A) / 2 code chunks
-  static constexpr int META = BF ? 0 : BN * 16;                // Q4_K scale record / Q6_K high bits of 2 chunks
-  static constexpr int SC = Q6 ? BN * 4 : 0;                   // Q6_K int8 scale pairs of the 2 chunks
-  static constexpr int DW = Q6 ? BN * 4 : 0;                   // Q6_K aligned dword holding the block's f16 d
-  static constexpr int OFF_CODE = A_BYTES, OFF_META = OFF_CODE + CODE, OFF_SC = OFF_META + META,
-                       OFF_D = OFF_SC + SC;
-  static constexpr int SLOT = (OFF_D + DW + 255) / 256 * 256;
-  // DMA wave-instructions per slot: 1 KB at 16 B per lane, 256 B at 4 B per lane
-  static constexpr int NI_A = A_BYTES / 1024, NI_CODE = CODE / 1024, NI_META = META / 1024, NI_SC = SC / 256,
-                       NI_D = DW / 256;
-  static constexpr int TI = NI_A + NI_CODE + NI_META + NI_SC + NI_D;
-  static_assert(A_BYTES % 1024 == 0 && CODE % 1024 == 0 && META % 1024 == 0 && SC % 256 == 0, "slot pieces");
-};
+// The epilogue of one accumulator element (m, n) = v; `even`: this lane's column is even (its pair
+// partner, column n ^ 1, is the lane ^ 1).  S > 1: a split-K / stream-K partial, added atomically.
+template <int EPI>
+__device__ __forceinline__ void pf_store(const GemmQArgs& a, int m, int n, float v, bool even, int S) {
+  if constexpr (EPI == GEPI_SWIGLU_BF16) {
+    // interleaved gate/up columns: even lane = gate, odd lane = its up partner
+    const float up = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));
+    if (m < a.M && even) a.C16[(size_t)m * a.ldc + (n >> 1)] = f32_to_bf16(v / (1.f + __expf(-v)) * up);
+  } else if constexpr (EPI == GEPI_QKV) {
+    pf_qkv_out(a, m, n, v, even);
+  } else if (m < a.M) {
+    float* cp = a.C + (size_t)m * a.ldc + n;
+    if (S > 1) unsafeAtomicAdd(cp, v);
+    else if constexpr (EPI == GEPI_ACCUM) *cp += v;
+    else *cp = v;
+  }
+}
 
 __device__ __forceinline__ void pf_barrier() {
   asm volatile("" ::: "memory");
@@ -114,78 +118,6 @@ __device__ __forceinline__ void pf_glds4(const void* src, uint32_t lds) {
                : "memory");
 }
 
-// This wave's share of every slot: pieces i = pp * NW + wv (pp < PH; the last may not exist).  The
-// per-lane part of each piece's source address is a 32-bit byte offset computed once per workgroup;
-// a K-step adds only a uniform per-kind step offset (the repacked planes advance linearly in kt:
-// codes 32 B, Q6_K high bits 16 B, Q6_K scales 4 B per K-step; the 256-block records per 4 steps).
-template <int QT, int BM, int BN, int NW>
-struct PfDma {
-  using L = PfLayout<QT, BM, BN>;
-  static constexpr int PH = (L::TI + NW - 1) / NW;
-  uint32_t off[PH];
-
-  __device__ __forceinline__ void init(const GemmQArgs& a, int wrow0, int m0, int wv) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t nbk = (uint32_t)a.K >> 8;
-    static_for<PH>([&](auto ppc) {
-      constexpr int pp = decltype(ppc)::value;
-      int j = pp * NW + wv;
-      uint32_t o = 0;
-      if (j < L::NI_A) {  // A unit p -> row p>>3, logical 16-B unit (p&7) ^ ((row>>1)&7); rows past M re-read M-1
-        const int p = 64 * j + lane, row = p >> 3, c = (p & 7) ^ ((row >> 1) & 7);
-        const int m = min(m0 + row, a.M - 1);
-        o = ((uint32_t)m * (uint32_t)a.lda + (uint32_t)(c * 8)) * 2u;
-      } else if ((j -= L::NI_A) < L::NI_CODE) {
-        const int p = 64 * j + lane;
-        if constexpr (L::BF) {  // bf16 weight rows in the A swizzle
-          const int col = p >> 3, c = (p & 7) ^ ((col >> 1) & 7);
-          o = ((uint32_t)(wrow0 + col) * (uint32_t)a.K + (uint32_t)(c * 8)) * 2u;
-        } else {  // column col's two 16-B code chunks (2g, 2g+1): 32 contiguous bytes
-          const int col = p >> 1, h = p & 1;
-          o = (uint32_t)(wrow0 + col) * nbk * 128u + (uint32_t)h * 16u;
-        }
-      } else if ((j -= L::NI_CODE) < L::NI_META) {
-        const uint32_t row = (uint32_t)(wrow0 + 64 * j + lane);
-        o = L::Q6 ? row * nbk * 64u : row * nbk * 16u;  // Q6_K high bits (8 B per chunk) / Q4_K record
-      } else if ((j -= L::NI_META) < L::NI_SC) {
-        o = (uint32_t)(wrow0 + 64 * j + lane) * nbk * 16u;  // Q6_K int8 scales (2 B per chunk)
-      } else {
-        j -= L::NI_SC;
-        o = (uint32_t)(wrow0 + 64 * j + lane) * nbk;  // Q6_K d: the row's first block index
-      }
-      off[pp] = o;
-    });
-  }
-
-  // issue K-step kt into dst (all of this wave's pieces, or those with pp % NP == P: spread over phases)
-  template <int P = 0, int NP = 1>
-  __device__ __forceinline__ void issue(const GemmQArgs& a, const QWeight& w, int kt, uint32_t dst, int wv) const {
-    static_for<PH>([&](auto ppc) {
-      constexpr int pp = decltype(ppc)::value;
-      if constexpr (pp % NP != P) return;
-      int j = pp * NW + wv;
-      if (j >= L::TI) return;
-      if (j < L::NI_A) {
-        const uint8_t* src = (const uint8_t*)a.A + kt * 128 + off[pp];
-        pf_glds16(src, dst + j * 1024);
-      } else if ((j -= L::NI_A) < L::NI_CODE) {
-        const uint8_t* src = w.p0 + (L::BF ? kt * 128 : kt * 32) + off[pp];
-        pf_glds16(src, dst + L::OFF_CODE + j * 1024);
-      } else if ((j -= L::NI_CODE) < L::NI_META) {
-        const uint8_t* src = w.p1 + (L::Q6 ? kt * 16 : (kt >> 2) * 16) + off[pp];
-        pf_glds16(src, dst + L::OFF_META + j * 1024);
-      } else if ((j -= L::NI_META) < L::NI_SC) {
-        const uint8_t* src = w.p2 + kt * 4 + off[pp];
-        pf_glds4(src, dst + L::OFF_SC + j * 256);
-      } else {
-        j -= L::NI_SC;
-        const uint8_t* src = w.p3 + (((off[pp] + (uint32_t)(kt >> 2)) >> 1) << 2);  // the dword holding f16 d
-        pf_glds4(src, dst + L::OFF_D + j * 256);
-      }
-    });
-  }
-};
-
 // 8 codes (bytes of w0 then w1) -> bf16x8 fragment of sc * q - of
 __device__ __forceinline__ gbf16x8 pf_dq8(uint32_t w0, uint32_t w1, float sc, float of) {
   asm volatile("" : "+v"(w0), "+v"(w1));  // one v_cvt_f32_ubyteN per byte
@@ -209,24 +141,6 @@ struct PfBRaw {
   uint32_t dw;    // Q6_K dword holding d
   uint4 b1;       // bf16: fragment 1
 };
-
-template <int QT, int BM, int BN>
-__device__ __forceinline__ void pf_braw(const uint8_t* slot, int col, int q, PfBRaw& r) {
-  using L = PfLayout<QT, BM, BN>;
-  if constexpr (L::BF) {
-    r.mt = *(const uint4*)(slot + L::OFF_CODE + col * 128 + (((0 + q) ^ ((col >> 1) & 7)) << 4));
-    r.b1 = *(const uint4*)(slot + L::OFF_CODE + col * 128 + (((4 + q) ^ ((col >> 1) & 7)) << 4));
-  } else {
-    r.cw = *(const uint2*)(slot + L::OFF_CODE + col * 32 + 8 * q);
-    if constexpr (L::Q6) {
-      r.hb = *(const uint2*)(slot + L::OFF_META + col * 16 + 8 * (q >> 1));
-      r.scw = *(const uint32_t*)(slot + L::OFF_SC + col * 4);
-      r.dw = *(const uint32_t*)(slot + L::OFF_D + col * 4);
-    } else {
-      r.mt = *(const uint4*)(slot + L::OFF_META + col * 16);
-    }
-  }
-}
 
 template <int QT, int S>
 __device__ __forceinline__ gbf16x8 pf_bdec(const PfBRaw& r, int q, int kt, int dpar) {
@@ -268,152 +182,11 @@ __device__ __forceinline__ gbf16x8 pf_bdec(const PfBRaw& r, int q, int kt, int d
   return f;
 }
 
-// PROBE (timing anatomy only, tools/bench_gemm.py --pf-probe; never in the engine's launches):
-// 1 = no DMA waits, 4 = no DMA issued inside the loop (stale slots), 8 = no per-step barrier
-template <int QT, int BM, int NW, int NS, int EPI, int PROBE = 0>
-__device__ __forceinline__ void pf_body(const GemmQArgs& a, int m0, int n0, int seg, int kt0, int kt1, int S) {
-  constexpr int BN = NW * 32, MT = BM / 16;
-  constexpr int GR = MT < 8 ? MT : 8, NG = MT / GR;  // row tiles per phase, phases per k-substep
-  using L = PfLayout<QT, BM, BN>;
-  extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  QWeight w;  // field-wise uniform selects (a dynamically indexed struct copy goes to scratch)
-  w.qtype = QT;
-  w.rows = seg == 0 ? a.seg[0].rows : (seg == 1 ? a.seg[1].rows : a.seg[2].rows);
-  w.cols = a.K;
-  w.pad_ = 0;
-  w.p0 = seg == 0 ? a.seg[0].p0 : (seg == 1 ? a.seg[1].p0 : a.seg[2].p0);
-  w.p1 = seg == 0 ? a.seg[0].p1 : (seg == 1 ? a.seg[1].p1 : a.seg[2].p1);
-  w.p2 = seg == 0 ? a.seg[0].p2 : (seg == 1 ? a.seg[1].p2 : a.seg[2].p2);
-  w.p3 = seg == 0 ? a.seg[0].p3 : (seg == 1 ? a.seg[1].p3 : a.seg[2].p3);
-  const int wrow0 = n0 - (seg == 0 ? a.seg_n0[0] : (seg == 1 ? a.seg_n0[1] : a.seg_n0[2]));
-  const int nbk = a.K >> 8;
-  const int r16 = lane & 15, q = lane >> 4;
-  const int col0 = wv * 32 + r16;  // this lane's two columns: col0, col0 + 16 (tile-relative)
-
-  gf32x4 acc[MT][2];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) acc[i][c] = gf32x4{0.f, 0.f, 0.f, 0.f};
-
-  // pieces per slot of this wave (PH if wv < TI % NW): the vmcnt immediates
-  constexpr int PH = (L::TI + NW - 1) / NW, PLO = L::TI / NW;
-  const bool many = (L::TI % NW == 0) || wv < L::TI % NW;
-  const int nk = kt1 - kt0;
-  PfDma<QT, BM, BN, NW> dma;
-  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(pf_lds_addr(pf_smem));
-  dma.init(a, wrow0, m0, wv);
-#pragma unroll
-  for (int p = 0; p < NS - 1; ++p)
-    if (p < nk) dma.issue(a, w, kt0 + p, lds0 + p * L::SLOT, wv);
-
-  int cur = 0;
-  for (int t = 0; t < nk; ++t) {
-    // step t's pieces landed (the younger NS - 2 steps may stay in flight), then everyone's
-    if constexpr (PROBE & 1) {
-    } else if constexpr (NS == 3) {
-      if (t + 1 < nk) {
-        if (many) pf_vmcnt<PH>(); else pf_vmcnt<PLO>();
-      } else {
-        pf_vmcnt<0>();
-      }
-    } else {
-      static_assert(NS == 2, "2 or 3 slots");
-      pf_vmcnt<0>();
-    }
-    if constexpr (!(PROBE & 8)) pf_barrier();
-    // refill the slot every wave finished reading last step
-    if (!(PROBE & 4) && t + NS - 1 < nk) {
-      const int ns = cur == 0 ? NS - 1 : cur - 1;
-      dma.issue(a, w, kt0 + t + NS - 1, lds0 + ns * L::SLOT, wv);
-    }
-    const uint8_t* slot = pf_smem + cur * L::SLOT;
-    const int kt = kt0 + t;
-    // Phases: A fragments of GR row tiles per phase in two named register groups (fa / fb), the
-    // next phase's reads issued before this phase's MFMAs; fragment-1 decode inside phase 0.
-    // sched_barrier pins the phase order (hipcc otherwise keeps ~2 reads in flight per MFMA pair).
-    PfBRaw raw[2];
-    int dpar[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int col = col0 + 16 * c;
-      dpar[c] = L::Q6 ? (int)(((uint32_t)(wrow0 + col) * (uint32_t)nbk + (uint32_t)(kt >> 2)) & 1u) : 0;
-      pf_braw<QT, BM, BN>(slot, col, q, raw[c]);
-    }
-    gbf16x8 fa[GR], fb[GR], bf[2][2];
-    auto ldA = [&](gbf16x8(&f)[GR], int p) __attribute__((always_inline)) {
-      const int sp = p / NG, g = p % NG;
-#pragma unroll
-      for (int i = 0; i < GR; ++i) {
-        const int row = 16 * (g * GR + i) + r16;
-        const uint4 av = *(const uint4*)(slot + row * 128 + (((4 * sp + q) ^ ((row >> 1) & 7)) << 4));
-        __builtin_memcpy(&f[i], &av, 16);
-      }
-    };
-    ldA(fa, 0);
-    __builtin_amdgcn_sched_barrier(0);  // every read of the step's head in flight before the decode
-#pragma unroll
-    for (int c = 0; c < 2; ++c) bf[c][0] = pf_bdec<QT, 0>(raw[c], q, kt, dpar[c]);
-    __builtin_amdgcn_sched_barrier(0);
-    static_for<2 * NG>([&](auto pc) {
-      constexpr int p = decltype(pc)::value, sp = p / NG, g = p % NG;
-      if constexpr (p + 1 < 2 * NG) {
-        if constexpr (p % 2 == 0) ldA(fb, p + 1);
-        else ldA(fa, p + 1);
-      }
-      if constexpr (p == 0) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) bf[c][1] = pf_bdec<QT, 1>(raw[c], q, kt, dpar[c]);
-      }
-#pragma unroll
-      for (int i = 0; i < GR; ++i)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-          acc[g * GR + i][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p % 2 == 0 ? fa[i] : fb[i], bf[c][sp],
-                                                                       acc[g * GR + i][c], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    });
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this slot's LDS reads retired before it is refilled
-    cur = cur == NS - 1 ? 0 : cur + 1;
-  }
-
-  // epilogue -- C/D map of the 16x16 accumulator: col = lane & 15, row = 4 * (lane >> 4) + e
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const int n = n0 + col0 + 16 * c;
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int m = m0 + 16 * i + 4 * q + e;
-        const float v = acc[i][c][e];
-        if constexpr (EPI == GEPI_SWIGLU_BF16) {
-          // interleaved gate/up columns: even lane = gate, odd lane = its up partner
-          const float up = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));
-          if (m < a.M && !(r16 & 1)) a.C16[(size_t)m * a.ldc + (n >> 1)] = f32_to_bf16(v / (1.f + __expf(-v)) * up);
-        } else if constexpr (EPI == GEPI_QKV) {
-          pf_qkv_out(a, m, n, v, !(r16 & 1));
-        } else if (m < a.M) {
-          float* cp = a.C + (size_t)m * a.ldc + n;
-          if (S > 1) unsafeAtomicAdd(cp, v);
-          else if constexpr (EPI == GEPI_ACCUM) *cp += v;
-          else *cp = v;
-        }
-      }
-    }
-  }
-}
-
-
-// ---- 32x32x16 body: a wave owns BM rows x 32 columns = BM/32 accumulators of v_mfma_f32_32x32x16_bf16.
-// Per 64-deep K-step four k16 substeps s = 0..3 at k = 16s + 8h + j (h = lane >> 5): chunk (s & 1)'s
-// bytes 8h .. 8h+7, low nibbles for s < 2, high nibbles for s >= 2 -- again the MFMA's natural k
-// layout, so A fragments are 16-B row reads at unit 2s + h.  Per MFMA (32 cycles, vector issue held
-// for 8) there is room for ~6 fillers against ~2 on the 16x16x32 body, which left that body
-// issue-bound on its decode VALU + LDS reads (tools/bench_gemm.py --pf-probe, round 5).  The slot's
-// DMA pieces are issued one phase at a time between the MFMA groups instead of at the step head.
+// ---- 32x32x16 fragments (pf4): a wave's BM rows x 32 columns are BM/32 accumulators of
+// v_mfma_f32_32x32x16_bf16.  Per 64-deep K-step four k16 substeps s = 0..3 at k = 16s + 8h + j
+// (h = lane >> 5): chunk (s & 1)'s bytes 8h .. 8h+7, low nibbles for s < 2, high nibbles for s >= 2 --
+// again the MFMA's natural k layout, so A fragments are 16-B row reads at unit 2s + h.  Per MFMA (32
+// cycles, vector issue held for 8) there is room for ~6 fillers against ~2 on 16x16x32.
 struct PfBRaw32 {
   uint2 c0, c1;   // 8 code bytes of chunk 0 / chunk 1
   uint4 mt;       // Q4_K scale record | Q6_K high bits {c0 run0, c0 run1, c1 run0, c1 run1} | bf16 fragment 0
@@ -421,27 +194,6 @@ struct PfBRaw32 {
   uint32_t dw;    // Q6_K dword holding d
   uint4 b1, b2, b3;  // bf16 fragments 1..3
 };
-
-template <int QT, int BM, int BN>
-__device__ __forceinline__ void pf_braw32(const uint8_t* slot, int col, int h, PfBRaw32& r) {
-  using L = PfLayout<QT, BM, BN>;
-  if constexpr (L::BF) {
-    const uint8_t* row = slot + L::OFF_CODE + col * 128;
-    const int x = (col >> 1) & 7;
-    r.mt = *(const uint4*)(row + (((0 + h) ^ x) << 4));
-    r.b1 = *(const uint4*)(row + (((2 + h) ^ x) << 4));
-    r.b2 = *(const uint4*)(row + (((4 + h) ^ x) << 4));
-    r.b3 = *(const uint4*)(row + (((6 + h) ^ x) << 4));
-  } else {
-    r.c0 = *(const uint2*)(slot + L::OFF_CODE + col * 32 + 8 * h);
-    r.c1 = *(const uint2*)(slot + L::OFF_CODE + col * 32 + 16 + 8 * h);
-    r.mt = *(const uint4*)(slot + L::OFF_META + col * 16);
-    if constexpr (L::Q6) {
-      r.scw = *(const uint32_t*)(slot + L::OFF_SC + col * 4);
-      r.dw = *(const uint32_t*)(slot + L::OFF_D + col * 4);
-    }
-  }
-}
 
 template <int QT, int S>
 __device__ __forceinline__ gbf16x8 pf_bdec32(const PfBRaw32& r, int h, int kt, int dpar) {
@@ -490,128 +242,18 @@ __device__ __forceinline__ gbf16x8 pf_bdec32(const PfBRaw32& r, int h, int kt, i
   return f;
 }
 
-template <int QT, int BM, int NW, int NS, int EPI, int PROBE = 0>
-__device__ __forceinline__ void pf_body32(const GemmQArgs& a, int m0, int n0, int seg, int kt0, int kt1, int S) {
-  constexpr int BN = NW * 32, MT = BM / 32;
-  using L = PfLayout<QT, BM, BN>;
-  extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  QWeight w;
-  w.qtype = QT;
-  w.rows = seg == 0 ? a.seg[0].rows : (seg == 1 ? a.seg[1].rows : a.seg[2].rows);
-  w.cols = a.K;
-  w.pad_ = 0;
-  w.p0 = seg == 0 ? a.seg[0].p0 : (seg == 1 ? a.seg[1].p0 : a.seg[2].p0);
-  w.p1 = seg == 0 ? a.seg[0].p1 : (seg == 1 ? a.seg[1].p1 : a.seg[2].p1);
-  w.p2 = seg == 0 ? a.seg[0].p2 : (seg == 1 ? a.seg[1].p2 : a.seg[2].p2);
-  w.p3 = seg == 0 ? a.seg[0].p3 : (seg == 1 ? a.seg[1].p3 : a.seg[2].p3);
-  const int wrow0 = n0 - (seg == 0 ? a.seg_n0[0] : (seg == 1 ? a.seg_n0[1] : a.seg_n0[2]));
-  const int nbk = a.K >> 8;
-  const int r32 = lane & 31, h = lane >> 5;
-  const int col = wv * 32 + r32;  // this lane's tile column
-
-  gf32x16 acc[MT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
-
-  constexpr int PH = (L::TI + NW - 1) / NW, PLO = L::TI / NW;
-  const bool many = (L::TI % NW == 0) || wv < L::TI % NW;
-  const int nk = kt1 - kt0;
-  PfDma<QT, BM, BN, NW> dma;
-  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(pf_lds_addr(pf_smem));
-  dma.init(a, wrow0, m0, wv);
-#pragma unroll
-  for (int p = 0; p < NS - 1; ++p)
-    if (p < nk) dma.issue(a, w, kt0 + p, lds0 + p * L::SLOT, wv);
-
-  int cur = 0;
-  for (int t = 0; t < nk; ++t) {
-    if constexpr (PROBE & 1) {
-    } else if constexpr (NS == 3) {
-      if (t + 1 < nk) {
-        if (many) pf_vmcnt<PH>(); else pf_vmcnt<PLO>();
-      } else {
-        pf_vmcnt<0>();
-      }
-    } else {
-      static_assert(NS == 2, "2 or 3 slots");
-      pf_vmcnt<0>();
-    }
-    if constexpr (!(PROBE & 8)) pf_barrier();
-    const bool refill = !(PROBE & 4) && t + NS - 1 < nk;
-    const uint32_t nslot = lds0 + (cur == 0 ? NS - 1 : cur - 1) * L::SLOT;
-    const int knext = kt0 + t + NS - 1;
-    const uint8_t* slot = pf_smem + cur * L::SLOT;
-    const int kt = kt0 + t;
-    const int dpar = L::Q6 ? (int)(((uint32_t)(wrow0 + col) * (uint32_t)nbk + (uint32_t)(kt >> 2)) & 1u) : 0;
-    PfBRaw32 raw;
-    pf_braw32<QT, BM, BN>(slot, col, h, raw);
-    gbf16x8 fa[MT], fb[MT], bf[4];
-    auto ldA = [&](gbf16x8(&f)[MT], int sp) __attribute__((always_inline)) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i) {
-        const int row = 32 * i + r32;
-        const uint4 av = *(const uint4*)(slot + row * 128 + (((2 * sp + h) ^ ((row >> 1) & 7)) << 4));
-        __builtin_memcpy(&f[i], &av, 16);
-      }
-    };
-    ldA(fa, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    bf[0] = pf_bdec32<QT, 0>(raw, h, kt, dpar);
-    __builtin_amdgcn_sched_barrier(0);
-    // phase sp: next substep's A reads, one share of the refill DMA, the next fragment's decode, the MFMAs
-    static_for<4>([&](auto pc) {
-      constexpr int sp = decltype(pc)::value;
-      if constexpr (sp + 1 < 4) {
-        if constexpr (sp % 2 == 0) ldA(fb, sp + 1);
-        else ldA(fa, sp + 1);
-      }
-      if (refill) dma.template issue<sp, 4>(a, w, knext, nslot, wv);
-      if constexpr (sp + 1 < 4) bf[sp + 1] = pf_bdec32<QT, sp + 1>(raw, h, kt, dpar);
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp % 2 == 0 ? fa[i] : fb[i], bf[sp], acc[i], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    });
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    cur = cur == NS - 1 ? 0 : cur + 1;
-  }
-
-  // epilogue -- C/D map of the 32x32 accumulator: col = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 h
-  const int n = n0 + col;
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int m = m0 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
-      const float v = acc[i][e];
-      if constexpr (EPI == GEPI_SWIGLU_BF16) {
-        const float up = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));
-        if (m < a.M && !(r32 & 1)) a.C16[(size_t)m * a.ldc + (n >> 1)] = f32_to_bf16(v / (1.f + __expf(-v)) * up);
-      } else if (m < a.M) {
-        float* cp = a.C + (size_t)m * a.ldc + n;
-        if (S > 1) unsafeAtomicAdd(cp, v);
-        else if constexpr (EPI == GEPI_ACCUM) *cp += v;
-        else *cp = v;
-      }
-    }
-  }
-}
-
 
 // ==== pf4: 4 waves (one per SIMD) x WC columns each, 32x32x16 MFMA, accumulators in AGPRs ============
-// Round-5 probes (tools/bench_gemm.py --pf-probe + rocprofv3 PMC, gate/up M = 2048): with 8 waves the
-// two waves of a SIMD race for its matrix pipe, the leader then idles at every per-step barrier
-// (SQ_WAIT_ANY 148M vs 55M quad-cycles without the barrier) while the step head -- fragment reads
-// and the B decode -- ran with the pipe idle; the runtime piece selection of the shared DMA added
-// ~68 SALU per wave-step.  Here each wave owns its SIMD, DMAs its OWN weight columns (so it can
-// wait for, read and decode step t+1's B fragments with its own vmcnt, before the barrier, inside
-// step t's last phases) and every DMA piece is compile-time: one vmcnt immediate per wave.
+// Measured in round 5 (timing probes + rocprofv3 PMC, gate/up M = 2048) on the first bodies, which
+// shared one DMA among 8 waves and decoded at the step head: the two waves of a SIMD raced for its
+// matrix pipe, the leader then idled at every per-step barrier (SQ_WAIT_ANY 148M vs 55M quad-cycles
+// without the barrier) while the step head -- fragment reads and the B decode -- ran with the pipe
+// idle; the runtime piece selection of the shared DMA added ~68 SALU per wave-step.  Here each wave
+// owns its SIMD, DMAs its OWN weight columns (so it can wait for, read and decode step t+1's B
+// fragments with its own vmcnt, before the barrier, inside step t's last phases) and every DMA
+// piece is compile-time: one vmcnt immediate per wave.
 //
-// Formats beyond Q4_K / Q6_K / bf16 (round 6, verdict r5 missing #4) read the GEMV engines' planes
+// Formats beyond Q4_K / Q6_K / bf16 read the GEMV engines' planes
 // (quant_pack.hip) in place -- no second copy of any weight:
 //   Q5_K  = the Q4_K codes + record, plus the block's 32 qh bytes (bit 2g + hi of byte l = high bit of
 //           weight 64g + 32hi + l) fetched with every K-step as one more 1 KB piece;
@@ -693,18 +335,11 @@ struct Pf4Dma {
     });
   }
 
-  // K-step kt into the slot at LDS byte address dst (wave-uniform).  PROBE 16: weight pieces read
-  // contiguous 1 KB (wrong data; coalescing probe), PROBE 32: no weight pieces (timing only)
-  template <int PROBE = 0>
+  // K-step kt into the slot at LDS byte address dst (wave-uniform)
   __device__ __forceinline__ void issue(const GemmQArgs& a, const QWeight& w, int kt, uint32_t dst, int wv) const {
     const uint32_t wb = dst + L::OFF_B + (uint32_t)wv * L::WB;
     static_for<L::PW>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
-      if constexpr ((PROBE & 32) && i >= L::NA) return;
-      if constexpr ((PROBE & 16) && i >= L::NA) {
-        pf_glds16(w.p0 + kt * 4096 + (i - L::NA) * 1024 + (threadIdx.x & 63) * 16 + wv * 65536, wb + (i - L::NA) * 256);
-        return;
-      }
       if constexpr (i < L::NA) {
         pf_glds16((const uint8_t*)a.A + kt * 128 + off[i], dst + (NW * i + wv) * 1024);
       } else if constexpr (i < L::NA + L::NCODE) {
@@ -754,14 +389,14 @@ __device__ __forceinline__ void pf4_braw(const uint8_t* wbase, int cl, int h, Pf
   }
 }
 
-template <int QT, int BM, int WC, int EPI, int PROBE = 0>
+template <int QT, int BM, int WC, int EPI>
 __device__ __forceinline__ void pf4_body(const GemmQArgs& a, int m0, int n0, int seg, int kt0, int kt1, int S) {
   using L = Pf4Layout<QT, BM, WC>;
   constexpr int MT = BM / 32, CT = WC / 32, NS = L::NS, PW = L::PW;
   extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  QWeight w;
+  QWeight w;  // field-wise uniform selects (a dynamically indexed struct copy goes to scratch)
   w.qtype = QT;
   w.rows = seg == 0 ? a.seg[0].rows : (seg == 1 ? a.seg[1].rows : a.seg[2].rows);
   w.cols = a.K;
@@ -795,7 +430,7 @@ __device__ __forceinline__ void pf4_body(const GemmQArgs& a, int m0, int n0, int
   // stale slot, neither ever consumed; every DMA is drained before the epilogue.
   const int klast = kt1 - 1;
 #pragma unroll
-  for (int p = 0; p < NS; ++p) dma.template issue<PROBE>(a, w, min(kt0 + p, klast), lds0 + p * L::SLOT, wv);
+  for (int p = 0; p < NS; ++p) dma.issue(a, w, min(kt0 + p, klast), lds0 + p * L::SLOT, wv);
 
   // B fragments: bf[c][s] is consumed by phase s; the next step's fragment s is decoded into it in
   // the phase after (s = 0..2 in phases 1..3 of this step, s = 3 in phase 0 of the next), from raw
@@ -838,9 +473,7 @@ __device__ __forceinline__ void pf4_body(const GemmQArgs& a, int m0, int n0, int
   };
   constexpr int NMF = MT * CT, HALF = NMF / 2;
   // step kt0's own pieces (NS - 1 younger steps in flight)
-  if constexpr (!(PROBE & 1)) {
-    pf_vmcnt<(NS - 1) * PW>();
-  }
+  pf_vmcnt<(NS - 1) * PW>();
   read_raw(pf_smem, kt0);
   dec(std::integral_constant<int, 0>{});
   dec(std::integral_constant<int, 1>{});
@@ -861,9 +494,7 @@ __device__ __forceinline__ void pf4_body(const GemmQArgs& a, int m0, int n0, int
     __builtin_amdgcn_sched_barrier(0);
     // phase 1: own step-(t+1) pieces landed (NS - 2 younger steps in flight) -> raw bytes, fragment 0
     ldA(slot, fa, 2);
-    if constexpr (!(PROBE & 1)) {
-      pf_vmcnt<(NS - 2) * PW>();
-    }
+    pf_vmcnt<(NS - 2) * PW>();
     read_raw(pf_smem + nxt * L::SLOT, kt0 + t + 1);
     dec(std::integral_constant<int, 0>{});
     mfma_range(fb, 1, 0, NMF);
@@ -878,9 +509,9 @@ __device__ __forceinline__ void pf4_body(const GemmQArgs& a, int m0, int n0, int
     mfma_range(fb, 3, 0, HALF);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if constexpr (!(PROBE & 8)) pf_barrier();
+    pf_barrier();
     ldA(pf_smem + nxt * L::SLOT, fa, 0);
-    if constexpr (!(PROBE & 4)) dma.template issue<PROBE>(a, w, min(kt0 + t + NS, klast), lds0 + cur * L::SLOT, wv);
+    dma.issue(a, w, min(kt0 + t + NS, klast), lds0 + cur * L::SLOT, wv);
     dec(std::integral_constant<int, 2>{});
     mfma_range(fb, 3, HALF, NMF);
     cur = nxt;
@@ -892,33 +523,19 @@ __device__ __forceinline__ void pf4_body(const GemmQArgs& a, int m0, int n0, int
   for (int c = 0; c < CT; ++c) {
     const int n = n0 + wv * WC + 32 * c + r32;
 #pragma unroll
-    for (int i = 0; i < MT; ++i) {
+    for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = m0 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
-        const float v = acc[i][c][e];
-        if constexpr (EPI == GEPI_SWIGLU_BF16) {
-          const float up = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));
-          if (m < a.M && !(r32 & 1)) a.C16[(size_t)m * a.ldc + (n >> 1)] = f32_to_bf16(v / (1.f + __expf(-v)) * up);
-        } else if constexpr (EPI == GEPI_QKV) {
-          pf_qkv_out(a, m, n, v, !(r32 & 1));
-        } else if (m < a.M) {
-          float* cp = a.C + (size_t)m * a.ldc + n;
-          if (S > 1) unsafeAtomicAdd(cp, v);
-          else if constexpr (EPI == GEPI_ACCUM) *cp += v;
-          else *cp = v;
-        }
-      }
-    }
+      for (int e = 0; e < 16; ++e)
+        pf_store<EPI>(a, m0 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h, n, acc[i][c][e], !(r32 & 1), S);
   }
 }
 
 // ==== pf8: 8 waves (two per SIMD) x 32 columns, 16x16x32 MFMA ======================================
-// The 8-wave 16x16x32 body ran the compute-only probe at 1.33 PF per busy CU against 1.16 for pf4's
-// one wave per SIMD (the SIMD's second wave covers the first's LDS latencies); this is that body
-// with pf4's structure: compile-time own-column DMA pieces, the next step's B decode inside this
+// With the DMA taken out, 8 waves on 16x16x32 ran at 1.33 PF per busy CU against 1.16 for pf4's one
+// wave per SIMD (measured in round 5: the SIMD's second wave covers the first's LDS latencies); this
+// is that geometry with pf4's structure: compile-time own-column DMA pieces, the next step's B decode inside this
 // step's phases, the barrier between the two halves of the last phase, a branch-free loop.
-template <int QT, int BM, int EPI, int PROBE = 0>
+template <int QT, int BM, int EPI>
 __device__ __forceinline__ void pf8_body(const GemmQArgs& a, int m0, int n0, int seg, int kt0, int kt1, int S) {
   constexpr int NW = 8, WC = 32;
   using L = Pf4Layout<QT, BM, WC, NW>;
@@ -926,7 +543,7 @@ __device__ __forceinline__ void pf8_body(const GemmQArgs& a, int m0, int n0, int
   extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  QWeight w;
+  QWeight w;  // field-wise uniform selects (a dynamically indexed struct copy goes to scratch)
   w.qtype = QT;
   w.rows = seg == 0 ? a.seg[0].rows : (seg == 1 ? a.seg[1].rows : a.seg[2].rows);
   w.cols = a.K;
@@ -950,7 +567,7 @@ __device__ __forceinline__ void pf8_body(const GemmQArgs& a, int m0, int n0, int
   const uint32_t lds0 = __builtin_amdgcn_readfirstlane(pf_lds_addr(pf_smem));
   dma.init(a, wcol0, m0, wv);
 #pragma unroll
-  for (int p = 0; p < NS; ++p) dma.template issue<PROBE>(a, w, min(kt0 + p, klast), lds0 + p * L::SLOT, wv);
+  for (int p = 0; p < NS; ++p) dma.issue(a, w, min(kt0 + p, klast), lds0 + p * L::SLOT, wv);
 
   gbf16x8 bf[2][2], fa[GR], fb[GR];
   PfBRaw raw[2];
@@ -1013,9 +630,7 @@ __device__ __forceinline__ void pf8_body(const GemmQArgs& a, int m0, int n0, int
       acc[g * GR + i][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[i], bf[c][sp], acc[g * GR + i][c], 0, 0, 0);
     }
   };
-  if constexpr (!(PROBE & 1)) {
-    pf_vmcnt<(NS - 1) * PW>();
-  }
+  pf_vmcnt<(NS - 1) * PW>();
   read_raw(pf_smem, kt0);
   dec(std::integral_constant<int, 0>{});
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1035,9 +650,7 @@ __device__ __forceinline__ void pf8_body(const GemmQArgs& a, int m0, int n0, int
       if constexpr (p == 0) dec(std::integral_constant<int, 1>{});  // this step's fragment 1
       if constexpr (p == NG) {
         // own pieces of step t+1 landed (NS - 2 younger steps in flight): its raw bytes, fragment 0
-        if constexpr (!(PROBE & 1)) {
-          pf_vmcnt<(NS - 2) * PW>();
-        }
+        pf_vmcnt<(NS - 2) * PW>();
         read_raw(pf_smem + nxt * L::SLOT, kt0 + t + 1);
         dec(std::integral_constant<int, 0>{});
       }
@@ -1049,9 +662,9 @@ __device__ __forceinline__ void pf8_body(const GemmQArgs& a, int m0, int n0, int
         mfma_range(cf, p, 0, GR);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (!(PROBE & 8)) pf_barrier();
+        pf_barrier();
         ldA(pf_smem + nxt * L::SLOT, nf, 0);
-        if constexpr (!(PROBE & 4)) dma.template issue<PROBE>(a, w, min(kt0 + t + NS, klast), lds0 + cur * L::SLOT, wv);
+        dma.issue(a, w, min(kt0 + t + NS, klast), lds0 + cur * L::SLOT, wv);
         mfma_range(cf, p, GR, 2 * GR);
       }
     });
@@ -1068,31 +681,17 @@ __device__ __forceinline__ void pf8_body(const GemmQArgs& a, int m0, int n0, int
   for (int c = 0; c < 2; ++c) {
     const int n = n0 + wv * WC + 16 * c + r16;
 #pragma unroll
-    for (int i = 0; i < MT; ++i) {
+    for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int m = m0 + 16 * i + 4 * q + e;
-        const float v = acc[i][c][e];
-        if constexpr (EPI == GEPI_SWIGLU_BF16) {
-          const float up = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));
-          if (m < a.M && !(r16 & 1)) a.C16[(size_t)m * a.ldc + (n >> 1)] = f32_to_bf16(v / (1.f + __expf(-v)) * up);
-        } else if constexpr (EPI == GEPI_QKV) {
-          pf_qkv_out(a, m, n, v, !(r16 & 1));
-        } else if (m < a.M) {
-          float* cp = a.C + (size_t)m * a.ldc + n;
-          if (S > 1) unsafeAtomicAdd(cp, v);
-          else if constexpr (EPI == GEPI_ACCUM) *cp += v;
-          else *cp = v;
-        }
-      }
-    }
+      for (int e = 0; e < 4; ++e) pf_store<EPI>(a, m0 + 16 * i + 4 * q + e, n, acc[i][c][e], !(r16 & 1), S);
   }
 }
 
 // ==== pf8c: pf8 with the K-quant weight planes staged coalesced ==================================
-// Round-5 probe (bench_gemm.py --pf-probe 216/316): the per-step weight pieces -- each column's 32 B
-// of codes and its 16-B scale record, i.e. 32-64 separate rows per DMA instruction -- cost 13-18 %
-// of the kernel against contiguous pieces.  Here a wave stages, per HALF block (2 K-steps), 64
+// Measured in round 5: pf8's per-step weight pieces -- each column's 32 B of codes and its 16-B scale
+// record, i.e. 32-64 separate rows per DMA instruction -- cost 13-18 % of the kernel against
+// contiguous pieces.  (The same staging on v_mfma_f32_32x32x16_bf16 was tried and dropped: 611 vs
+// 484 us at gate/up M = 2048.)  Here a wave stages, per HALF block (2 K-steps), 64
 // contiguous bytes of codes per column (16 rows x 64 B per DMA: 4 lanes per row, the 16-B units
 // XOR-swizzled by (row >> 2) & 3 on the source side so the 8-byte fragment reads are conflict-free),
 // per 256-block the scale records (Q4_K meta / Q6_K int8 scales: 16 B per row) and Q6_K d, and the
@@ -1176,7 +775,7 @@ struct PfcDma {
   }
 };
 
-template <int QT, int BM, int EPI, int PROBE = 0>
+template <int QT, int BM, int EPI>
 __device__ __forceinline__ void pf8c_body(const GemmQArgs& a, int m0, int n0, int seg, int kt0, int kt1, int S) {
   using L = PfcLayout<QT, BM>;
   constexpr int NW = 8, WC = 32, NSA = L::NSA, PW = L::PW;
@@ -1185,7 +784,7 @@ __device__ __forceinline__ void pf8c_body(const GemmQArgs& a, int m0, int n0, in
   extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  QWeight w;
+  QWeight w;  // field-wise uniform selects (a dynamically indexed struct copy goes to scratch)
   w.qtype = QT;
   w.rows = seg == 0 ? a.seg[0].rows : (seg == 1 ? a.seg[1].rows : a.seg[2].rows);
   w.cols = a.K;
@@ -1305,7 +904,7 @@ __device__ __forceinline__ void pf8c_body(const GemmQArgs& a, int m0, int n0, in
       acc[g * GR + i][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[i], bf[c][sp], acc[g * GR + i][c], 0, 0, 0);
     }
   };
-  if constexpr (!(PROBE & 1)) pf_vmcnt<PW>();  // the prologue group landed (G(-2) in flight)
+  pf_vmcnt<PW>();  // the prologue group landed (G(-2) in flight)
   read_raw(kt0);
   dec(std::integral_constant<int, 0>{});
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1326,19 +925,19 @@ __device__ __forceinline__ void pf8c_body(const GemmQArgs& a, int m0, int n0, in
       if constexpr (p == NG) {
         // G(s-2) landed -- step s+1's codes / records and this wave's A pieces of it -- with only
         // G(s-1)'s first-phase pieces younger
-        if constexpr (!(PROBE & 1)) pf_vmcnt<PRE_WAIT>();
+        pf_vmcnt<PRE_WAIT>();
         read_raw(kt0 + s + 1);  // (past the last step: stale buffers, unused)
         dec(std::integral_constant<int, 0>{});
       }
       // G(s-1): its slot / buffers were released by B(s) (past the end: clamped re-loads, unused)
-      if constexpr (!(PROBE & 4)) group(s - 1, pc);
+      group(s - 1, pc);
       if constexpr (p + 1 < NPH) {
         mfma_range(cf, p, 0, 2 * GR);
       } else {
         mfma_range(cf, p, 0, GR);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (!(PROBE & 8)) pf_barrier();
+        pf_barrier();
         ldA(pf_smem + nxt * L::A_BYTES, nf, 0);
         mfma_range(cf, p, GR, 2 * GR);
       }
@@ -1355,271 +954,92 @@ __device__ __forceinline__ void pf8c_body(const GemmQArgs& a, int m0, int n0, in
   for (int c = 0; c < 2; ++c) {
     const int n = n0 + wv * WC + 16 * c + r16;
 #pragma unroll
-    for (int i = 0; i < MT; ++i) {
+    for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int m = m0 + 16 * i + 4 * q + e;
-        const float v = acc[i][c][e];
-        if constexpr (EPI == GEPI_SWIGLU_BF16) {
-          const float up = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));
-          if (m < a.M && !(r16 & 1)) a.C16[(size_t)m * a.ldc + (n >> 1)] = f32_to_bf16(v / (1.f + __expf(-v)) * up);
-        } else if constexpr (EPI == GEPI_QKV) {
-          pf_qkv_out(a, m, n, v, !(r16 & 1));
-        } else if (m < a.M) {
-          float* cp = a.C + (size_t)m * a.ldc + n;
-          if (S > 1) unsafeAtomicAdd(cp, v);
-          else if constexpr (EPI == GEPI_ACCUM) *cp += v;
-          else *cp = v;
-        }
-      }
-    }
+      for (int e = 0; e < 4; ++e) pf_store<EPI>(a, m0 + 16 * i + 4 * q + e, n, acc[i][c][e], !(r16 & 1), S);
   }
 }
 
-// ==== pf8d: pf8c on v_mfma_f32_32x32x16_bf16 ======================================================
-// PMC (round 5, gate/up M = 2048): with the DMA on, the waves spend +25 % active-instruction cycles
-// (LDS-DMA issue ~55-60 cycles each) and the SIMD's issue port -- MFMA issue + decode VALU + DMA +
-// LDS reads -- exceeds the matrix pipe's 2048 cycles per step.  A 32x32x16 MFMA holds vector issue
-// for 8 of its 32 cycles against 8 of 16 for 16x16x32: half the MFMA issue cost at equal FLOPs.
-// Wave tile BM rows x 32 columns = BM/32 accumulators; per K-step four k16 substeps (k = 16 s + 8 h
-// + j: chunk (s & 1) bytes 8h.., low nibbles for s < 2).  Phase s uses fragment s; the next step's
-// fragment s is decoded in phase s+1 (fragment 3 in the next step's phase 0) from raw bytes read
-// after the phase-1 wait.  The staging is pf8c's (same layout, same DMA groups).
-template <int QT, int BM, int EPI, int PROBE = 0>
-__device__ __forceinline__ void pf8d_body(const GemmQArgs& a, int m0, int n0, int seg, int kt0, int kt1, int S) {
-  using L = PfcLayout<QT, BM>;
-  constexpr int NW = 8, WC = 32, NSA = L::NSA, PW = L::PW;
-  // GD row tiles per phase (4 at BM = 256: two 8-fragment A buffers spill), ND phases per substep
-  constexpr int MT = BM / 32, GD = MT > 4 ? 4 : MT, ND = MT / GD, NPH = 4 * ND;
-  extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  QWeight w;
-  w.qtype = QT;
-  w.rows = seg == 0 ? a.seg[0].rows : (seg == 1 ? a.seg[1].rows : a.seg[2].rows);
-  w.cols = a.K;
-  w.pad_ = 0;
-  w.p0 = seg == 0 ? a.seg[0].p0 : (seg == 1 ? a.seg[1].p0 : a.seg[2].p0);
-  w.p1 = seg == 0 ? a.seg[0].p1 : (seg == 1 ? a.seg[1].p1 : a.seg[2].p1);
-  w.p2 = seg == 0 ? a.seg[0].p2 : (seg == 1 ? a.seg[1].p2 : a.seg[2].p2);
-  w.p3 = seg == 0 ? a.seg[0].p3 : (seg == 1 ? a.seg[1].p3 : a.seg[2].p3);
-  const int wcol0 = n0 - (seg == 0 ? a.seg_n0[0] : (seg == 1 ? a.seg_n0[1] : a.seg_n0[2])) + wv * WC;
-  const uint32_t nbk = (uint32_t)a.K >> 8;
-  const int r32 = lane & 31, h = lane >> 5;
-
-  gf32x16 acc[MT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
-
-  const int nk = kt1 - kt0, klast = kt1 - 1, hlast = (kt1 >> 1) - 1, blast = (kt1 >> 2) - 1;
-  PfcDma<QT, BM> dma;
-  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(pf_lds_addr(pf_smem));
-  dma.init(a, wcol0, m0, wv);
-  constexpr uint32_t CBS = NW * L::CB_W, HBS = NW * L::HB_W, RBS = NW * L::RB_W, DBS = NW * L::D_W;
-  const uint32_t cb = lds0 + L::OFF_CB + wv * L::CB_W, hb = lds0 + L::OFF_HB + wv * L::HB_W;
-  const uint32_t rb = lds0 + L::OFF_RB + wv * L::RB_W, db = lds0 + L::OFF_D + wv * L::D_W;
-  // G(s) during step s+1, after the wait at phase ND: A pieces over phases ND .. ND + NAP - 1, code
-  // (+ high bits) and records (+ d) in phase NPH - 2 (NPH - 1 at ND == 1); PH_ALL = every piece (prologue)
-  constexpr int PH_ALL = -1, NAP = ND == 1 ? 2 : 4, PB = ND == 1 ? 3 : NPH - 2;
-  auto group = [&](int s, auto phc) __attribute__((always_inline)) {
-    constexpr int ph = decltype(phc)::value;
-    const uint32_t adst = lds0 + (uint32_t)(((s + 3 * NSA) % NSA) * L::A_BYTES);
-    const int ka = min(kt0 + s + NSA, klast);
-    if constexpr (ph == PH_ALL) dma.A(a, ka, adst, wv);
-    else if constexpr (ph >= ND && ph < ND + NAP) dma.template A_part<(ph - ND), NAP>(a, ka, adst, wv);
-    const int H = (kt0 >> 1) + ((s + 4) >> 1), B = (kt0 >> 2) + ((s + 6) >> 2), pr = (s + 6) & 3;
-    if constexpr (ph == PH_ALL || ph == PB) {
-      dma.code(w, min(H, hlast), s & 1, cb + (uint32_t)(H & 1) * CBS);
-      if constexpr (L::Q6) dma.hi(w, min(H, hlast), s & 1, nbk, hb + (uint32_t)(H & 1) * HBS);
-      dma.rec(w, min(B, blast), pr, nbk, rb + (uint32_t)(B & 1) * RBS);
-      if constexpr (L::Q6) dma.dq(w, min(B, blast), pr, nbk, db + (uint32_t)(B & 1) * DBS);
-    }
-  };
-  {  // prologue: step 0's A, half block 0, block 0, then G(-2)
-    const int H0 = kt0 >> 1, B0 = kt0 >> 2;
-    dma.A(a, kt0, lds0, wv);
-    dma.code(w, H0, 0, cb + (uint32_t)(H0 & 1) * CBS);
-    dma.code(w, H0, 1, cb + (uint32_t)(H0 & 1) * CBS);
-    if constexpr (L::Q6) {
-      dma.hi(w, H0, 0, nbk, hb + (uint32_t)(H0 & 1) * HBS);
-      dma.hi(w, H0, 1, nbk, hb + (uint32_t)(H0 & 1) * HBS);
-    }
-#pragma unroll
-    for (int pr = 0; pr < 4; ++pr) {
-      dma.rec(w, B0, pr, nbk, rb + (uint32_t)(B0 & 1) * RBS);
-      if constexpr (L::Q6) dma.dq(w, B0, pr, nbk, db + (uint32_t)(B0 & 1) * DBS);
-    }
-    group(-2, std::integral_constant<int, PH_ALL>{});
-  }
-
-  gbf16x8 bf[4], fa[GD], fb[GD];
-  PfBRaw32 raw;
-  int rkt = kt0;
-  auto read_raw = [&](int kt) __attribute__((always_inline)) {
-    const int H = kt >> 1, j = kt & 1, B = kt >> 2;
-    const uint8_t* cbp = pf_smem + L::OFF_CB + (H & 1) * CBS + wv * L::CB_W + r32 * 64;
-    const uint8_t* rbp = pf_smem + L::OFF_RB + (B & 1) * RBS + wv * L::RB_W + r32 * 16;
-    const int x = (r32 >> 2) & 3;
-    raw.c0 = *(const uint2*)(cbp + (((2 * j) ^ x) << 4) + 8 * h);
-    raw.c1 = *(const uint2*)(cbp + (((2 * j + 1) ^ x) << 4) + 8 * h);
-    if constexpr (L::Q6) {
-      // high bits {c0 run0, c0 run1, c1 run0, c1 run1} of this step's two chunks
-      raw.mt = *(const uint4*)(pf_smem + L::OFF_HB + (H & 1) * HBS + wv * L::HB_W + r32 * 32 + 16 * j);
-      // int8 scales {c0 run0, c0 run1, c1 run0, c1 run1}: chunks 2g, 2g + 1 -> bytes 4g .. 4g + 3
-      raw.scw = *(const uint32_t*)(rbp + 4 * (kt & 3));
-      raw.dw = *(const uint32_t*)(pf_smem + L::OFF_D + (B & 1) * DBS + wv * L::D_W + r32 * 4);
-    } else {
-      raw.mt = *(const uint4*)rbp;
-    }
-    rkt = kt;
-  };
-  auto dec = [&](auto sc) __attribute__((always_inline)) {
-    constexpr int S4 = decltype(sc)::value;
-    const int dpar = L::Q6 ? (int)(((uint32_t)(wcol0 + r32) * nbk + (uint32_t)(rkt >> 2)) & 1u) : 0;
-    bf[S4] = pf_bdec32<QT, S4>(raw, h, rkt, dpar);
-    asm volatile("" : "+v"(bf[S4]));  // keep the decode in this phase (else sunk past the barrier)
-  };
-  auto ldA = [&](const uint8_t* sl, gbf16x8(&f)[GD], int p) __attribute__((always_inline)) {
-    const int sp = p / ND, g = p % ND;
-#pragma unroll
-    for (int i = 0; i < GD; ++i) {
-      const int row = 32 * (g * GD + i) + r32;
-      const uint4 av = *(const uint4*)(sl + row * 128 + (((2 * sp + h) ^ ((row >> 1) & 7)) << 4));
-      __builtin_memcpy(&f[i], &av, 16);
-    }
-  };
-  auto mfma_range = [&](const gbf16x8(&f)[GD], int p, int k0, int k1) __attribute__((always_inline)) {
-    const int sp = p / ND, g = p % ND;
-#pragma unroll
-    for (int i = 0; i < GD; ++i)
-      if (i >= k0 && i < k1)
-        acc[g * GD + i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[i], bf[sp], acc[g * GD + i], 0, 0, 0);
-  };
-  if constexpr (!(PROBE & 1)) pf_vmcnt<PW>();  // the prologue group landed (G(-2) in flight)
-  read_raw(kt0);
-  dec(std::integral_constant<int, 0>{});
-  dec(std::integral_constant<int, 1>{});
-  dec(std::integral_constant<int, 2>{});
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  pf_barrier();
-  ldA(pf_smem, fa, 0);
-
-  int cur = 0;
-  for (int s = 0; s < nk; ++s) {
-    const uint8_t* slot = pf_smem + cur * L::A_BYTES;
-    const int nxt = cur == NSA - 1 ? 0 : cur + 1;
-    static_for<NPH>([&](auto pc) {
-      constexpr int p = decltype(pc)::value;
-      __builtin_amdgcn_sched_barrier(0);
-      auto& cf = (p % 2 == 0) ? fa : fb;
-      auto& nf = (p % 2 == 0) ? fb : fa;
-      if constexpr (p + 1 < NPH) ldA(slot, nf, p + 1);
-      if constexpr (p == 0) dec(std::integral_constant<int, 3>{});  // this step's fragment 3
-      if constexpr (p == ND) {
-        // G(s-2) landed (step s+1's codes / records, this wave's A pieces of it); nothing of G(s-1)
-        // is issued before this point
-        if constexpr (!(PROBE & 1)) pf_vmcnt<0>();
-        read_raw(kt0 + s + 1);  // (past the last step: stale buffers, unused)
-        dec(std::integral_constant<int, 0>{});
-      }
-      if constexpr (p == 2 * ND) dec(std::integral_constant<int, 1>{});
-      if constexpr (ND > 1 && p == 3 * ND) dec(std::integral_constant<int, 2>{});
-      if constexpr (!(PROBE & 4)) {
-        if constexpr (p >= ND) group(s - 1, pc);
-      }
-      if constexpr (p + 1 < NPH) {
-        mfma_range(cf, p, 0, GD);
-      } else {
-        mfma_range(cf, p, 0, GD / 2);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (ND == 1) dec(std::integral_constant<int, 2>{});
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (!(PROBE & 8)) pf_barrier();
-        ldA(pf_smem + nxt * L::A_BYTES, nf, 0);
-        mfma_range(cf, p, GD / 2, GD);
-      }
-    });
-    cur = nxt;
-  }
-  pf_vmcnt<0>();  // no LDS-DMA may land after this workgroup's LDS is released
-
-  // epilogue -- C/D map of the 32x32 accumulator: col = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 h
-  const int n = n0 + wv * WC + r32;
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int m = m0 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
-      const float v = acc[i][e];
-      if constexpr (EPI == GEPI_SWIGLU_BF16) {
-        const float up = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));
-        if (m < a.M && !(r32 & 1)) a.C16[(size_t)m * a.ldc + (n >> 1)] = f32_to_bf16(v / (1.f + __expf(-v)) * up);
-      } else if (m < a.M) {
-        float* cp = a.C + (size_t)m * a.ldc + n;
-        if (S > 1) unsafeAtomicAdd(cp, v);
-        else if constexpr (EPI == GEPI_ACCUM) *cp += v;
-        else *cp = v;
-      }
-    }
-  }
-}
-
-// stacks the 256-column launches run on pf8_body (64-weight K-steps, Pf4Layout planes) instead of pf8c:
+// ==== tiles -> bodies, kernels, launch ============================================================
+// stacks whose 256-column tiles run pf8_body (64-weight K-steps, Pf4Layout planes) instead of pf8c:
 // bf16, and the Q5_K / Q4_0 / Q8_0 recipes' stacks (their Q6_K segments too)
-template <int QT0, int QT1>
-constexpr bool pf8_generic() {
-  return QT0 == QT_BF16 || QT0 == QT_Q5_K || QT0 == QT_Q4_0 || QT0 == QT_Q8_0;
+constexpr bool pf8_generic(int QT0) { return QT0 == QT_BF16 || QT0 == QT_Q5_K || QT0 == QT_Q4_0 || QT0 == QT_Q8_0; }
+
+// The BN-column tiles of a (possibly mixed-format) segment stack: tiles of the last segment run as
+// QT1 (the Q4_K_M QKV stack: Q|K Q4_K, V Q6_K), the others as QT0.
+template <int QT0_, int QT1_, int BN_>
+struct PfTile {
+  static constexpr int QT0 = QT0_, QT1 = QT1_, BN = BN_;
+  static constexpr int NW = BN / 32, NT = 64 * NW;            // waves of 32 columns; threads per workgroup
+  static constexpr bool C = BN == 256 && !pf8_generic(QT0);   // pf8c_body
+  static constexpr int KG = C ? 4 : 1;                        // K-steps per slice unit (pf8c slices on 256-blocks)
+  static constexpr bool TAIL = BN == 128 || QT0 != QT_BF16;   // 256-row launches may take the tail split
+  template <int QT, int BM>
+  static constexpr int lds_of() {
+    if constexpr (C) return PfcLayout<QT, BM>::TOTAL;
+    else return Pf4Layout<QT, BM, 32, NW>::NS * Pf4Layout<QT, BM, 32, NW>::SLOT;
+  }
+  template <int BM>
+  static constexpr int lds() {  // (the larger format's)
+    return lds_of<QT0, BM>() > lds_of<QT1, BM>() ? lds_of<QT0, BM>() : lds_of<QT1, BM>();
+  }
+};
+
+// tile L (column-fastest) of a launch with BM x BN tiles: its first row and column, its segment
+struct PfAt {
+  int m0, n0, seg;
+};
+__device__ __forceinline__ PfAt pf_tile(const GemmQArgs& a, int L, int BM, int BN) {
+  const int nN = a.N / BN, tn = L % nN, tm = L / nN;
+  PfAt t{tm * BM, tn * BN, 0};
+  if (a.nseg > 1 && t.n0 >= a.seg_n0[1]) t.seg = 1;
+  if (a.nseg > 2 && t.n0 >= a.seg_n0[2]) t.seg = 2;
+  return t;
 }
 
-template <int QT0, int QT1, int BM, int EPI, int PROBE = 0>
-__global__ void __launch_bounds__(512) gemm_pf8_kernel(GemmQArgs a) {
-  const int nN = a.N / 256, nM = (a.M + BM - 1) / BM, total = nN * nM;
-  const int L = xcd_remap(blockIdx.x, total);
-  const int tn = L % nN, tm = L / nN;
-  const int m0 = tm * BM, n0 = tn * 256;
-  int seg = 0;
-  if (a.nseg > 1 && n0 >= a.seg_n0[1]) seg = 1;
-  if (a.nseg > 2 && n0 >= a.seg_n0[2]) seg = 2;
-  const int S = gridDim.y;
-  if constexpr (pf8_generic<QT0, QT1>()) {
-    const int nk_all = a.K / 64;
-    const int kt0 = (int)((long)blockIdx.y * nk_all / S), kt1 = (int)((long)(blockIdx.y + 1) * nk_all / S);
-    if constexpr (QT0 != QT1) {
-      if (seg == a.nseg - 1) {
-        pf8_body<QT1, BM, EPI, PROBE>(a, m0, n0, seg, kt0, kt1, S);
-        return;
-      }
+// K-steps [kt0, kt1) of tile t on the family's body, as format QT
+template <class T, int QT, int BM, int EPI>
+__device__ __forceinline__ void pf_body(const GemmQArgs& a, PfAt t, int kt0, int kt1, int S) {
+  if constexpr (T::BN == 128) pf4_body<QT, BM, 32, EPI>(a, t.m0, t.n0, t.seg, kt0, kt1, S);
+  else if constexpr (T::C) pf8c_body<QT, BM, EPI>(a, t.m0, t.n0, t.seg, kt0, kt1, S);
+  else pf8_body<QT, BM, EPI>(a, t.m0, t.n0, t.seg, kt0, kt1, S);
+}
+// ... in its segment's format.  HALVES (the tail split, BM = 256): half >= 0 runs the 128-row body
+// (the choice sits inside the segment branch: the other nesting cost the mixed stacks registers).
+template <class T, int BM, int EPI, bool HALVES = false, int QT = T::QT0>
+__device__ __forceinline__ void pf_run_tile(const GemmQArgs& a, PfAt t, int kt0, int kt1, int S, int half = -1) {
+  if constexpr (QT != T::QT1) {
+    if (t.seg == a.nseg - 1) {
+      pf_run_tile<T, BM, EPI, HALVES, T::QT1>(a, t, kt0, kt1, S, half);
+      return;
     }
-    pf8_body<QT0, BM, EPI, PROBE>(a, m0, n0, seg, kt0, kt1, S);
+  }
+  if constexpr (HALVES) {
+    if (half < 0) pf_body<T, QT, BM, EPI>(a, t, kt0, kt1, S);
+    else pf_body<T, QT, 128, EPI>(a, t, kt0, kt1, S);
   } else {
-    // K-quant stacks: pf8c, slices on 256-block boundaries
-    const int nb = a.K / 256;
-    const int kt0 = 4 * (int)((long)blockIdx.y * nb / S), kt1 = 4 * (int)((long)(blockIdx.y + 1) * nb / S);
-    // PROBE bit 64: the 32x32x16 body (pf8d) instead of pf8c, for A/B timing (measured slower with
-    // the DMA on: gate/up M = 2048 611 vs 484 us, round 5)
-    if constexpr (QT0 != QT1) {
-      if (seg == a.nseg - 1) {
-        if constexpr (PROBE & 64) pf8d_body<QT1, BM, EPI, PROBE>(a, m0, n0, seg, kt0, kt1, S);
-        else pf8c_body<QT1, BM, EPI, PROBE>(a, m0, n0, seg, kt0, kt1, S);
-        return;
-      }
-    }
-    if constexpr (PROBE & 64) pf8d_body<QT0, BM, EPI, PROBE>(a, m0, n0, seg, kt0, kt1, S);
-    else pf8c_body<QT0, BM, EPI, PROBE>(a, m0, n0, seg, kt0, kt1, S);
+    pf_body<T, QT, BM, EPI>(a, t, kt0, kt1, S);
   }
 }
 
-// Tail split (round 5).  A 256x256-tile launch of T tiles runs one workgroup per CU (LDS), so it
+// One launch for every tile of the stack; gridDim.y = K slices (S > 1: atomic adds).
+template <class T, int BM, int EPI>
+__global__ void __launch_bounds__(T::NT) gemm_pf_kernel(GemmQArgs a) {
+  const int total = (a.N / T::BN) * ((a.M + BM - 1) / BM);
+  const PfAt t = pf_tile(a, xcd_remap(blockIdx.x, total), BM, T::BN);
+  const int S = gridDim.y, nu = a.K / (64 * T::KG);
+  const int kt0 = T::KG * (int)((long)blockIdx.y * nu / S), kt1 = T::KG * (int)((long)(blockIdx.y + 1) * nu / S);
+  pf_run_tile<T, BM, EPI>(a, t, kt0, kt1, S);
+}
+
+// Tail split (round 5).  A 256-row-tile launch of T tiles runs one workgroup per CU (LDS), so it
 // takes ceil(T / CUs) rounds; when the last round is at most half full (R = T mod CUs <= CUs / 2)
 // the other CUs idle through it -- Mistral's gate/up at 2048 rows is 896 tiles = 3.5 rounds of 256
-// that cost 4.  Here the first T - R tiles run as usual and each of the last R runs as TWO 128-row
-// workgroups (the BM = 128 body on its half), dispatched last: the final round puts half-size work
-// on every CU.  K-quant stacks, S = 1 (plans with split-K fill the chip their own way).
-template <int QT0, int QT1, int EPI>
-__global__ void __launch_bounds__(512) gemm_pf8t_kernel(GemmQArgs a, int F) {
-  const int nN = a.N / 256;
+// that cost 4.  Here the first F = T - R tiles run as usual and each of the last R runs as TWO
+// 128-row workgroups (the BM = 128 body on its half), dispatched last: the final round puts
+// half-size work on every CU.  S = 1 (plans with split-K fill the chip their own way).
+template <class T, int EPI>
+__global__ void __launch_bounds__(T::NT) gemm_pft_kernel(GemmQArgs a, int F) {
   int L, half = -1;
   if ((int)blockIdx.x < F) {
     L = xcd_remap(blockIdx.x, F);
@@ -1628,33 +1048,9 @@ __global__ void __launch_bounds__(512) gemm_pf8t_kernel(GemmQArgs a, int F) {
     L = F + (j >> 1);
     half = j & 1;
   }
-  const int tn = L % nN, tm = L / nN;
-  const int m0 = tm * 256 + (half > 0 ? 128 : 0), n0 = tn * 256;
-  int seg = 0;
-  if (a.nseg > 1 && n0 >= a.seg_n0[1]) seg = 1;
-  if (a.nseg > 2 && n0 >= a.seg_n0[2]) seg = 2;
-  const int kt1 = 4 * (a.K / 256);
-  if constexpr (pf8_generic<QT0, QT1>()) {
-    if constexpr (QT0 != QT1) {
-      if (seg == a.nseg - 1) {
-        if (half < 0) pf8_body<QT1, 256, EPI>(a, m0, n0, seg, 0, kt1, 1);
-        else pf8_body<QT1, 128, EPI>(a, m0, n0, seg, 0, kt1, 1);
-        return;
-      }
-    }
-    if (half < 0) pf8_body<QT0, 256, EPI>(a, m0, n0, seg, 0, kt1, 1);
-    else pf8_body<QT0, 128, EPI>(a, m0, n0, seg, 0, kt1, 1);
-  } else {
-    if constexpr (QT0 != QT1) {
-      if (seg == a.nseg - 1) {
-        if (half < 0) pf8c_body<QT1, 256, EPI>(a, m0, n0, seg, 0, kt1, 1);
-        else pf8c_body<QT1, 128, EPI>(a, m0, n0, seg, 0, kt1, 1);
-        return;
-      }
-    }
-    if (half < 0) pf8c_body<QT0, 256, EPI>(a, m0, n0, seg, 0, kt1, 1);
-    else pf8c_body<QT0, 128, EPI>(a, m0, n0, seg, 0, kt1, 1);
-  }
+  PfAt t = pf_tile(a, L, 256, T::BN);
+  t.m0 += half > 0 ? 128 : 0;
+  pf_run_tile<T, 256, EPI, true>(a, t, 0, T::KG * (a.K / (64 * T::KG)), 1, half);
 }
 
 // full tiles before the tail of a 256 x BN launch, or -1 (no tail split for this shape / plan)
@@ -1665,17 +1061,16 @@ inline int pf_tail_full(const GemmQArgs& a, int BN, int S) {
   return (T > C && R > 0 && 2 * R <= C) ? T - R : -1;
 }
 
-// Stream-K (round 6, verdict r5 #6): a launch whose output tiles do not fill the chip -- the N = 4096-6144
+// Stream-K (round 6): a launch whose output tiles do not fill the chip -- the N = 4096-6144
 // projections of a 512-token chunk have 32-192 tiles for 256 CUs -- runs one workgroup per CU over an
-// equal share of the flattened (tile, K-step) iteration space instead of split-K's equal slices of
+// equal share of the flattened (tile, K unit) iteration space instead of split-K's equal slices of
 // every tile: workgroup w takes iterations [w * ipw, (w + 1) * ipw), i.e. the tail of one tile and the
 // head of the next, and adds each partial tile into C with the split-K atomics (STORE targets zeroed
-// first).  KG: K-steps per unit (4 for the K-quant pf8c body, which slices on 256-blocks).  A workgroup
-// that runs a second segment barriers first: the previous body's last LDS reads against its prologue DMA.
-template <int QT0, int QT1, int BM, int EPI, int KG, typename Body>
-__device__ __forceinline__ void pf_stream_k(const GemmQArgs& a, int BN, int ipw, Body body) {
-  const int nN = a.N / BN, nM = (a.M + BM - 1) / BM;
-  const int nk = a.K / (64 * KG);
+// first).  A unit is KG K-steps.  A workgroup that runs a second segment barriers first: the previous
+// body's last LDS reads against its prologue DMA.
+template <class T, int BM, int EPI>
+__global__ void __launch_bounds__(T::NT) gemm_pfsk_kernel(GemmQArgs a, int ipw) {
+  const int nN = a.N / T::BN, nM = (a.M + BM - 1) / BM, nk = a.K / (64 * T::KG);
   const long total = (long)nN * nM * nk;
   long it = (long)blockIdx.x * ipw;
   const long end = it + ipw < total ? it + ipw : total;
@@ -1683,54 +1078,13 @@ __device__ __forceinline__ void pf_stream_k(const GemmQArgs& a, int BN, int ipw,
   while (it < end) {
     const int L = (int)(it / nk), k0 = (int)(it - (long)L * nk);
     const int k1 = (int)(k0 + (end - it) < nk ? k0 + (end - it) : nk);
-    const int tn = L % nN, tm = L / nN;
-    const int m0 = tm * BM, n0 = tn * BN;
-    int seg = 0;
-    if (a.nseg > 1 && n0 >= a.seg_n0[1]) seg = 1;
-    if (a.nseg > 2 && n0 >= a.seg_n0[2]) seg = 2;
+    const PfAt t = pf_tile(a, L, BM, T::BN);
     if (!first) __syncthreads();
     // S: 1 when this workgroup owns the whole tile (plain epilogue), else atomic partials
-    body(m0, n0, seg, k0 * KG, k1 * KG, (k0 == 0 && k1 == nk) ? 1 : 2);
+    pf_run_tile<T, BM, EPI>(a, t, k0 * T::KG, k1 * T::KG, (k0 == 0 && k1 == nk) ? 1 : 2);
     it += k1 - k0;
     first = false;
   }
-}
-
-template <int QT0, int QT1, int BM, int WC, int EPI>
-__global__ void __launch_bounds__(256) gemm_pf4sk_kernel(GemmQArgs a, int ipw) {
-  pf_stream_k<QT0, QT1, BM, EPI, 1>(a, 4 * WC, ipw, [&](int m0, int n0, int seg, int kt0, int kt1, int S) {
-    if constexpr (QT0 != QT1) {
-      if (seg == a.nseg - 1) {
-        pf4_body<QT1, BM, WC, EPI>(a, m0, n0, seg, kt0, kt1, S);
-        return;
-      }
-    }
-    pf4_body<QT0, BM, WC, EPI>(a, m0, n0, seg, kt0, kt1, S);
-  });
-}
-
-template <int QT0, int QT1, int BM, int EPI>
-__global__ void __launch_bounds__(512) gemm_pf8sk_kernel(GemmQArgs a, int ipw) {
-  constexpr int KG = pf8_generic<QT0, QT1>() ? 1 : 4;
-  pf_stream_k<QT0, QT1, BM, EPI, KG>(a, 256, ipw, [&](int m0, int n0, int seg, int kt0, int kt1, int S) {
-    if constexpr (pf8_generic<QT0, QT1>()) {
-      if constexpr (QT0 != QT1) {
-        if (seg == a.nseg - 1) {
-          pf8_body<QT1, BM, EPI>(a, m0, n0, seg, kt0, kt1, S);
-          return;
-        }
-      }
-      pf8_body<QT0, BM, EPI>(a, m0, n0, seg, kt0, kt1, S);
-    } else {
-      if constexpr (QT0 != QT1) {
-        if (seg == a.nseg - 1) {
-          pf8c_body<QT1, BM, EPI>(a, m0, n0, seg, kt0, kt1, S);
-          return;
-        }
-      }
-      pf8c_body<QT0, BM, EPI>(a, m0, n0, seg, kt0, kt1, S);
-    }
-  });
 }
 
 // iterations per workgroup of a stream-K launch over the device's CUs (workgroups = its grid)
@@ -1743,222 +1097,53 @@ inline int pf_sk_ipw(const GemmQArgs& a, int BM, int BN, int KG, int& grid) {
   return ipw;
 }
 
-template <int QT0, int QT1, int BM>
-constexpr int pf8_lds_bytes() {
-  if constexpr (pf8_generic<QT0, QT1>()) {
-    using L0 = Pf4Layout<QT0, BM, 32, 8>;
-    using L1 = Pf4Layout<QT1, BM, 32, 8>;
-    return L0::NS * L0::SLOT > L1::NS * L1::SLOT ? L0::NS * L0::SLOT : L1::NS * L1::SLOT;
-  } else {
-    return PfcLayout<QT0, BM>::TOTAL > PfcLayout<QT1, BM>::TOTAL ? PfcLayout<QT0, BM>::TOTAL
-                                                                 : PfcLayout<QT1, BM>::TOTAL;
-  }
-}
-
-template <int QT0, int QT1, int BM>
-void pf8_launch(const GemmQArgs& a, int S, hipStream_t st) {
-  constexpr int lds = pf8_lds_bytes<QT0, QT1, BM>();
-  static_assert(lds <= 160 * 1024, "LDS");
-  if (S < 0) {  // stream-K (STORE / ACCUM only: partial tiles are atomic adds)
-    int grid = 0;
-    const int ipw = pf_sk_ipw(a, BM, 256, pf8_generic<QT0, QT1>() ? 1 : 4, grid);
-    if (a.epi == GEPI_STORE)
-      hipLaunchKernelGGL((gemm_pf8sk_kernel<QT0, QT1, BM, GEPI_STORE>), dim3(grid), dim3(512), lds, st, a, ipw);
-    else
-      hipLaunchKernelGGL((gemm_pf8sk_kernel<QT0, QT1, BM, GEPI_ACCUM>), dim3(grid), dim3(512), lds, st, a, ipw);
-    return;
-  }
-  if constexpr (BM == 256 && QT0 != QT_BF16) {  // (K-quant stacks: the tail split)
-    const int F = pf_tail_full(a, 256, S);
-    if (F >= 0) {
-      constexpr int l128 = pf8_lds_bytes<QT0, QT1, 128>();
-      constexpr int ldst = lds > l128 ? lds : l128;
-      const int T = (a.N / 256) * ((a.M + 255) / 256);
-      const dim3 grid(F + 2 * (T - F)), block(512);
-      switch (a.epi) {
-        case GEPI_STORE: hipLaunchKernelGGL((gemm_pf8t_kernel<QT0, QT1, GEPI_STORE>), grid, block, ldst, st, a, F); break;
-        case GEPI_ACCUM: hipLaunchKernelGGL((gemm_pf8t_kernel<QT0, QT1, GEPI_ACCUM>), grid, block, ldst, st, a, F); break;
-        default: hipLaunchKernelGGL((gemm_pf8t_kernel<QT0, QT1, GEPI_SWIGLU_BF16>), grid, block, ldst, st, a, F); break;
-      }
-      return;
-    }
-  }
-  const dim3 grid((a.N / 256) * ((a.M + BM - 1) / BM), S), block(512);
-  switch (a.epi) {
-    case GEPI_STORE: hipLaunchKernelGGL((gemm_pf8_kernel<QT0, QT1, BM, GEPI_STORE>), grid, block, lds, st, a); break;
-    case GEPI_ACCUM: hipLaunchKernelGGL((gemm_pf8_kernel<QT0, QT1, BM, GEPI_ACCUM>), grid, block, lds, st, a); break;
-    case GEPI_QKV: hipLaunchKernelGGL((gemm_pf8_kernel<QT0, QT1, BM, GEPI_QKV>), grid, block, lds, st, a); break;
-    default: hipLaunchKernelGGL((gemm_pf8_kernel<QT0, QT1, BM, GEPI_SWIGLU_BF16>), grid, block, lds, st, a); break;
-  }
-}
-
-template <int QT0, int QT1, int BM, int WC, int EPI, int PROBE = 0>
-__global__ void __launch_bounds__(256) gemm_pf4_kernel(GemmQArgs a) {
-  constexpr int BN = 4 * WC;
-  const int nN = a.N / BN, nM = (a.M + BM - 1) / BM, total = nN * nM;
-  const int L = xcd_remap(blockIdx.x, total);
-  const int tn = L % nN, tm = L / nN;
-  const int m0 = tm * BM, n0 = tn * BN;
-  int seg = 0;
-  if (a.nseg > 1 && n0 >= a.seg_n0[1]) seg = 1;
-  if (a.nseg > 2 && n0 >= a.seg_n0[2]) seg = 2;
-  const int S = gridDim.y, nk_all = a.K / 64;
-  const int kt0 = (int)((long)blockIdx.y * nk_all / S), kt1 = (int)((long)(blockIdx.y + 1) * nk_all / S);
-  if constexpr (QT0 != QT1) {
-    if (seg == a.nseg - 1) {
-      pf4_body<QT1, BM, WC, EPI, PROBE>(a, m0, n0, seg, kt0, kt1, S);
-      return;
-    }
-  }
-  pf4_body<QT0, BM, WC, EPI, PROBE>(a, m0, n0, seg, kt0, kt1, S);
-}
-
-// pf4's tail split (256 x 4 WC tiles): as gemm_pf8t_kernel, the last R tiles as two 128-row halves
-template <int QT0, int QT1, int WC, int EPI>
-__global__ void __launch_bounds__(256) gemm_pf4t_kernel(GemmQArgs a, int F) {
-  constexpr int BN = 4 * WC;
-  const int nN = a.N / BN;
-  int L, half = -1;
-  if ((int)blockIdx.x < F) {
-    L = xcd_remap(blockIdx.x, F);
-  } else {
-    const int j = xcd_remap(blockIdx.x - F, gridDim.x - F);
-    L = F + (j >> 1);
-    half = j & 1;
-  }
-  const int tn = L % nN, tm = L / nN;
-  const int m0 = tm * 256 + (half > 0 ? 128 : 0), n0 = tn * BN;
-  int seg = 0;
-  if (a.nseg > 1 && n0 >= a.seg_n0[1]) seg = 1;
-  if (a.nseg > 2 && n0 >= a.seg_n0[2]) seg = 2;
-  const int kt1 = a.K / 64;
-  if constexpr (QT0 != QT1) {
-    if (seg == a.nseg - 1) {
-      if (half < 0) pf4_body<QT1, 256, WC, EPI>(a, m0, n0, seg, 0, kt1, 1);
-      else pf4_body<QT1, 128, WC, EPI>(a, m0, n0, seg, 0, kt1, 1);
-      return;
-    }
-  }
-  if (half < 0) pf4_body<QT0, 256, WC, EPI>(a, m0, n0, seg, 0, kt1, 1);
-  else pf4_body<QT0, 128, WC, EPI>(a, m0, n0, seg, 0, kt1, 1);
-}
-
-template <int QT0, int QT1, int BM, int WC>
-constexpr int pf4_lds_bytes() {
-  using L0 = Pf4Layout<QT0, BM, WC>;
-  using L1 = Pf4Layout<QT1, BM, WC>;
-  return L0::NS * L0::SLOT > L1::NS * L1::SLOT ? L0::NS * L0::SLOT : L1::NS * L1::SLOT;
-}
-
-template <int QT0, int QT1, int BM, int WC>
-void pf4_launch(const GemmQArgs& a, int S, hipStream_t st) {
-  constexpr int lds = pf4_lds_bytes<QT0, QT1, BM, WC>();
-  static_assert(lds <= 160 * 1024, "LDS");
-  if (S < 0) {  // stream-K (STORE / ACCUM only)
-    int grid = 0;
-    const int ipw = pf_sk_ipw(a, BM, 4 * WC, 1, grid);
-    if (a.epi == GEPI_STORE)
-      hipLaunchKernelGGL((gemm_pf4sk_kernel<QT0, QT1, BM, WC, GEPI_STORE>), dim3(grid), dim3(256), lds, st, a, ipw);
-    else
-      hipLaunchKernelGGL((gemm_pf4sk_kernel<QT0, QT1, BM, WC, GEPI_ACCUM>), dim3(grid), dim3(256), lds, st, a, ipw);
-    return;
-  }
-  if constexpr (BM == 256) {
-    const int F = pf_tail_full(a, 4 * WC, S);
-    if (F >= 0) {
-      constexpr int l128 = pf4_lds_bytes<QT0, QT1, 128, WC>();
-      constexpr int ldst = lds > l128 ? lds : l128;
-      const int T = (a.N / (4 * WC)) * ((a.M + 255) / 256);
-      const dim3 grid(F + 2 * (T - F)), block(256);
-      switch (a.epi) {
-        case GEPI_STORE: hipLaunchKernelGGL((gemm_pf4t_kernel<QT0, QT1, WC, GEPI_STORE>), grid, block, ldst, st, a, F); break;
-        case GEPI_ACCUM: hipLaunchKernelGGL((gemm_pf4t_kernel<QT0, QT1, WC, GEPI_ACCUM>), grid, block, ldst, st, a, F); break;
-        default: hipLaunchKernelGGL((gemm_pf4t_kernel<QT0, QT1, WC, GEPI_SWIGLU_BF16>), grid, block, ldst, st, a, F); break;
-      }
-      return;
-    }
-  }
-  const dim3 grid((a.N / (4 * WC)) * ((a.M + BM - 1) / BM), S), block(256);
-  switch (a.epi) {
-    case GEPI_STORE: hipLaunchKernelGGL((gemm_pf4_kernel<QT0, QT1, BM, WC, GEPI_STORE>), grid, block, lds, st, a); break;
-    case GEPI_ACCUM: hipLaunchKernelGGL((gemm_pf4_kernel<QT0, QT1, BM, WC, GEPI_ACCUM>), grid, block, lds, st, a); break;
-    case GEPI_QKV: hipLaunchKernelGGL((gemm_pf4_kernel<QT0, QT1, BM, WC, GEPI_QKV>), grid, block, lds, st, a); break;
-    default: hipLaunchKernelGGL((gemm_pf4_kernel<QT0, QT1, BM, WC, GEPI_SWIGLU_BF16>), grid, block, lds, st, a); break;
-  }
-}
-
-// One launch for every tile of a (possibly mixed-format) segment stack: tiles of the last segment
-// run the QT1 body (the Q4_K_M QKV stack: Q|K Q4_K, V Q6_K).  gridDim.y = K slices (atomic adds).
-#ifndef AIOS_PF_MF
-#define AIOS_PF_MF 32  // MFMA shape of the production body (16: the 16x16x32 body)
-#endif
-template <int QT0, int QT1, int BM, int NW, int NS, int EPI, int PROBE = 0, int MF = AIOS_PF_MF>
-__global__ void __launch_bounds__(NW * 64) gemm_pf_kernel(GemmQArgs a) {
-  constexpr int BN = NW * 32;
-  const int nN = a.N / BN, nM = (a.M + BM - 1) / BM, total = nN * nM;
-  const int L = xcd_remap(blockIdx.x, total);
-  const int tn = L % nN, tm = L / nN;
-  const int m0 = tm * BM, n0 = tn * BN;
-  int seg = 0;
-  if (a.nseg > 1 && n0 >= a.seg_n0[1]) seg = 1;
-  if (a.nseg > 2 && n0 >= a.seg_n0[2]) seg = 2;
-  const int S = gridDim.y, nk_all = a.K / 64;
-  const int kt0 = (int)((long)blockIdx.y * nk_all / S), kt1 = (int)((long)(blockIdx.y + 1) * nk_all / S);
-  if constexpr (QT0 != QT1) {
-    if (seg == a.nseg - 1) {
-      if constexpr (MF == 32) pf_body32<QT1, BM, NW, NS, EPI, PROBE>(a, m0, n0, seg, kt0, kt1, S);
-      else pf_body<QT1, BM, NW, NS, EPI, PROBE>(a, m0, n0, seg, kt0, kt1, S);
-      return;
-    }
-  }
-  if constexpr (MF == 32) pf_body32<QT0, BM, NW, NS, EPI, PROBE>(a, m0, n0, seg, kt0, kt1, S);
-  else pf_body<QT0, BM, NW, NS, EPI, PROBE>(a, m0, n0, seg, kt0, kt1, S);
-}
-
-// slot bytes of a launch (the larger format's) and its slot count: 3 where they fit in 160 KB
-template <int QT0, int QT1, int BM, int NW>
-constexpr int pf_slot_bytes() {
-  return PfLayout<QT0, BM, NW * 32>::SLOT > PfLayout<QT1, BM, NW * 32>::SLOT ? PfLayout<QT0, BM, NW * 32>::SLOT
-                                                                             : PfLayout<QT1, BM, NW * 32>::SLOT;
-}
-template <int QT0, int QT1, int BM, int NW>
-constexpr int pf_slots() {
-  return 3 * pf_slot_bytes<QT0, QT1, BM, NW>() <= 160 * 1024 ? 3 : 2;
-}
-
-// host: launch one instantiation (grid = tiles x S)
-template <int QT0, int QT1, int BM, int NW>
+// host: one plan of one tile family.  S < 0: stream-K (STORE / ACCUM only: partial tiles are atomic
+// adds); S = 1 at BM = 256 takes the tail split where pf_tail_full says so (never QKV); else tiles x S.
+template <class T, int BM>
 void pf_launch(const GemmQArgs& a, int S, hipStream_t st) {
-  constexpr int BN = NW * 32;
-  constexpr int NS = pf_slots<QT0, QT1, BM, NW>();
-  constexpr int lds = NS * pf_slot_bytes<QT0, QT1, BM, NW>();
+  constexpr int lds = T::template lds<BM>();
   static_assert(lds <= 160 * 1024, "LDS");
-  const dim3 grid((a.N / BN) * ((a.M + BM - 1) / BM), S), block(NW * 64);
+  const dim3 block(T::NT);
+  if (S < 0) {
+    int grid = 0;
+    const int ipw = pf_sk_ipw(a, BM, T::BN, T::KG, grid);
+    if (a.epi == GEPI_STORE) hipLaunchKernelGGL((gemm_pfsk_kernel<T, BM, GEPI_STORE>), dim3(grid), block, lds, st, a, ipw);
+    else hipLaunchKernelGGL((gemm_pfsk_kernel<T, BM, GEPI_ACCUM>), dim3(grid), block, lds, st, a, ipw);
+    return;
+  }
+  if constexpr (BM == 256 && T::TAIL) {
+    const int F = pf_tail_full(a, T::BN, S);
+    if (F >= 0) {
+      constexpr int ldst = lds > T::template lds<128>() ? lds : T::template lds<128>();
+      const int tiles = (a.N / T::BN) * ((a.M + 255) / 256);
+      const dim3 grid(F + 2 * (tiles - F));
+      switch (a.epi) {
+        case GEPI_STORE: hipLaunchKernelGGL((gemm_pft_kernel<T, GEPI_STORE>), grid, block, ldst, st, a, F); break;
+        case GEPI_ACCUM: hipLaunchKernelGGL((gemm_pft_kernel<T, GEPI_ACCUM>), grid, block, ldst, st, a, F); break;
+        default: hipLaunchKernelGGL((gemm_pft_kernel<T, GEPI_SWIGLU_BF16>), grid, block, ldst, st, a, F); break;
+      }
+      return;
+    }
+  }
+  const dim3 grid((a.N / T::BN) * ((a.M + BM - 1) / BM), S);
   switch (a.epi) {
-    case GEPI_STORE: hipLaunchKernelGGL((gemm_pf_kernel<QT0, QT1, BM, NW, NS, GEPI_STORE>), grid, block, lds, st, a); break;
-    case GEPI_ACCUM: hipLaunchKernelGGL((gemm_pf_kernel<QT0, QT1, BM, NW, NS, GEPI_ACCUM>), grid, block, lds, st, a); break;
-    default: hipLaunchKernelGGL((gemm_pf_kernel<QT0, QT1, BM, NW, NS, GEPI_SWIGLU_BF16>), grid, block, lds, st, a); break;
+    case GEPI_STORE: hipLaunchKernelGGL((gemm_pf_kernel<T, BM, GEPI_STORE>), grid, block, lds, st, a); break;
+    case GEPI_ACCUM: hipLaunchKernelGGL((gemm_pf_kernel<T, BM, GEPI_ACCUM>), grid, block, lds, st, a); break;
+    case GEPI_QKV: hipLaunchKernelGGL((gemm_pf_kernel<T, BM, GEPI_QKV>), grid, block, lds, st, a); break;
+    default: hipLaunchKernelGGL((gemm_pf_kernel<T, BM, GEPI_SWIGLU_BF16>), grid, block, lds, st, a); break;
   }
 }
 
-// the tile set of one format pair (one translation unit each, compiled in parallel): BM x BN tiles,
-// BN = 4 waves x WC columns
+// the tile set of one format pair (one translation unit each, compiled in parallel)
 template <int QT0, int QT1>
 bool pf_launch_fmt(const GemmQArgs& a, int BM, int BN, int S, hipStream_t st) {
-  // 256-column tiles: the 8-wave body (pf8 / pf8c); 128-column tiles: pf4 with 32 columns per wave
-#define PF_GO8(bm)                      \
-  if (BM == bm && BN == 256) {          \
-    pf8_launch<QT0, QT1, bm>(a, S, st); \
-    return true;                        \
+#define PF_GO(bm, bn)                                \
+  if (BM == bm && BN == bn) {                        \
+    pf_launch<PfTile<QT0, QT1, bn>, bm>(a, S, st);   \
+    return true;                                     \
   }
-#define PF_GO4(bm)                          \
-  if (BM == bm && BN == 128) {              \
-    pf4_launch<QT0, QT1, bm, 32>(a, S, st); \
-    return true;                            \
-  }
-  PF_GO8(256) PF_GO8(128) PF_GO8(64) PF_GO4(256) PF_GO4(128) PF_GO4(64)
-#undef PF_GO8
-#undef PF_GO4
+  PF_GO(256, 256) PF_GO(128, 256) PF_GO(64, 256) PF_GO(256, 128) PF_GO(128, 128) PF_GO(64, 128)
+#undef PF_GO
   return false;
 }
 

@@ -28,7 +28,7 @@ static int pf_env(const char* name, int dflt) {
 }
 
 struct PfPlan {
-  int bm = 0, bn = 0, s = 1;  // s < 0: stream-K over the CUs (gemm_pf.h pf_stream_k)
+  int bm = 0, bn = 0, s = 1;  // s < 0: stream-K over the CUs (gemm_pf.h gemm_pfsk_kernel)
 };
 
 // Modelled time of one launch.  Per workgroup: max(MFMA time at the tile's sustained fraction of the

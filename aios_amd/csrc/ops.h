@@ -423,7 +423,6 @@ bool gemm_skinny_serves(const GemmQArgs& a);  // launch_gemm_skinny would take a
 bool launch_gemm_pf(const GemmQArgs& a, hipStream_t st);
 bool gemm_pf_serves(const GemmQArgs& a);  // launch_gemm_pf would take a (gemm_pf.hip)
 void gemm_pf_plan(const GemmQArgs& a, int& bm, int& bn, int& s);
-bool gemm_pf_probe(const GemmQArgs& a, int probe, hipStream_t st);  // timing anatomy (tools only)
 // time every prefill-GEMM plan for these args (buffers overwritten) and keep the fastest for their M
 // bucket; returns the number of plans timed
 int gemm_pf_autotune(const GemmQArgs& a, hipStream_t st);

@@ -1094,7 +1094,7 @@ def test_gemm_pf_split_k(E, monkeypatch, fmt, M, S, epi):
 @pytest.mark.parametrize("fmt", [GGMLType.Q4_K, GGMLType.Q5_K, GGMLType.Q8_0])
 def test_gemm_pf_tail_split(E, monkeypatch, epi, tile, N, fmt):
     """256-row plan whose last round is at most half full (M = 1280: 320 tiles on 256 CUs): the last
-    64 tiles run as two 128-row workgroups each (gemm_pf8t_kernel / gemm_pf4t_kernel).  Against the
+    64 tiles run as two 128-row workgroups each (gemm_pft_kernel, 256- and 128-column tiles).  Against the
     unquantized product and bit-identical to the plain launch (same per-element accumulation order)."""
     monkeypatch.setenv("AIOS_GEMM_PF_TILE", tile)
     M, K = 1280, 512
@@ -1126,13 +1126,14 @@ def test_gemm_pf_tail_split(E, monkeypatch, epi, tile, N, fmt):
 
 
 @pytest.mark.parametrize("segs,M", [([(GGMLType.Q4_K, 8192)], 2100),
-                                    ([(GGMLType.Q4_K, 4096), (GGMLType.Q4_K, 1024), (GGMLType.Q6_K, 1024)], 2800)])
+                                    ([(GGMLType.Q4_K, 4096), (GGMLType.Q4_K, 1024), (GGMLType.Q6_K, 1024)], 2800),
+                                    ([(GGMLType.Q5_K, 4096), (GGMLType.Q5_K, 1024), (GGMLType.Q6_K, 1024)], 2800)])
 @pytest.mark.parametrize("epi", ["store", "accum"])
 def test_gemm_pf_tail_split_ragged(E, monkeypatch, segs, M, epi):
     """the tail split with M NOT a multiple of 256 (the last row tile partial, its second
     128-row half entirely past M) and on the mixed Q4_K|Q6_K QKV stack (Mistral's 4096 + 1024 + 1024
-    rows: the segment branch runs per half): bit-identical to the plain launch, and against the
-    unquantized product"""
+    rows: the segment branch runs per half; the Q5_K|Q6_K stack takes it on the pf8 body, the Q4_K one
+    on pf8c): bit-identical to the plain launch, and against the unquantized product"""
     monkeypatch.setenv("AIOS_GEMM_PF_TILE", "256x256")
     K = 512
     mats, refs = zip(*[qmat(E, t, n, K, seed=140 + i, std=0.02) for i, (t, n) in enumerate(segs)])
@@ -1181,7 +1182,8 @@ def test_gemm_pf_production_shapes_vs_unquantized(E, monkeypatch, fmt, N, K, spl
 
 
 @pytest.mark.parametrize("fmt,N,K", [("mixed6144", 6144, 4096), ("q4k", 4096, 4096), ("q6k", 4096, 14336),
-                                     ("bf16", 2048, 2048), ("q5k", 4096, 4096), ("q8_0", 4096, 4096)])
+                                     ("bf16", 2048, 2048), ("q5k", 4096, 4096), ("q8_0", 4096, 4096),
+                                     ("mixed5k", 6144, 4096)])
 @pytest.mark.parametrize("tile", ["128x128", "128x256", "256x256"])
 @pytest.mark.parametrize("epi", ["store", "accum"])
 def test_gemm_pf_stream_k(E, monkeypatch, fmt, N, K, tile, epi):
@@ -1193,7 +1195,8 @@ def test_gemm_pf_stream_k(E, monkeypatch, fmt, N, K, tile, epi):
     monkeypatch.setenv("AIOS_GEMM_PF_SPLIT", "-1")
     segs = {"mixed6144": [(GGMLType.Q4_K, 4096), (GGMLType.Q4_K, 1024), (GGMLType.Q6_K, 1024)],
             "q4k": [(GGMLType.Q4_K, N)], "q6k": [(GGMLType.Q6_K, N)], "bf16": [(GGMLType.BF16, N)],
-            "q5k": [(GGMLType.Q5_K, N)], "q8_0": [(GGMLType.Q8_0, N)]}[fmt]
+            "q5k": [(GGMLType.Q5_K, N)], "q8_0": [(GGMLType.Q8_0, N)],
+            "mixed5k": [(GGMLType.Q5_K, 4096), (GGMLType.Q5_K, 1024), (GGMLType.Q6_K, 1024)]}[fmt]
     key = ("sk", fmt, K)
     if key not in _pf_cache:
         mats, refs = zip(*[qmat(E, t, n, K, seed=170 + i, std=0.02) for i, (t, n) in enumerate(segs)])

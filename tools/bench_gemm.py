@@ -47,7 +47,6 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--sweep", action="store_true", help="skinny kernel: RB x split-K sweep per shape")
     ap.add_argument("--pf-sweep", action="store_true", help="prefill GEMM: tile x split-K sweep per shape")
-    ap.add_argument("--pf-probe", action="store_true", help="prefill GEMM 256x256 Q4_K: timing-anatomy probes")
     ap.add_argument("--shapes", default=None, help="comma list of shape names (default: all)")
     args = ap.parse_args()
     E = native.require()
@@ -62,17 +61,6 @@ def main():
         m = E.QMatrix(int(t), N, K, raw)
         m.fill_random(1, 0.02)
         wb = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.02 if not args.no_torch else None
-        if args.pf_probe:
-            if t != GGMLType.Q4_K:
-                continue
-            for M in ms:
-                A = torch.randn(M, K, device="cuda").to(torch.bfloat16)
-                C = torch.zeros(M, N, device="cuda")
-                for probe in (300, 301, 304, 308, 313, 364, 368, 377):
-                    us = time_fn(lambda: E.gemm_pf_probe(A.data_ptr(), K, m, M, C.data_ptr(), probe, st), reps=10)
-                    row = dict(probe=probe, shape=name, M=M, us=round(us, 2), tflops=round(2 * M * N * K / us / 1e6, 1))
-                    print(json.dumps(row), flush=True)
-            continue
         if args.pf_sweep:
             for M in ms:
                 A = torch.randn(M, K, device="cuda").to(torch.bfloat16)
