@@ -377,6 +377,8 @@ PYBIND11_MODULE(_engine, m) {
       .def("reset_graphs", &Engine::reset_graphs)
       .def("copy_slot", &Engine::copy_slot, py::call_guard<py::gil_scoped_release>())
       .def("release_slot", &Engine::release_slot)
+      .def("shift_context", &Engine::shift_context, py::call_guard<py::gil_scoped_release>(), py::arg("slot"),
+           py::arg("n_tokens"), py::arg("n_keep"), py::arg("n_discard"))
       .def("block_table", &Engine::block_table)
       .def("kv_read",
            [](const Engine& e, int slot, int n_tokens) {

@@ -290,6 +290,18 @@ class Engine {
   // written again by either slot: writes un-share first), the partial last block copied
   void copy_slot(int src, int dst, int n_tokens);
   void release_slot(int slot);         // drop every block reference of the slot
+  // Context shift (ops.h KvShiftArgs: the rule): the slot's positions [n_keep + n_discard, n_tokens) move down
+  // by n_discard, K re-rotated, in place; returns the new length n_tokens - n_discard.  The blocks of
+  // [n_keep, new length) are mapped and un-shared first (a shared prefix block is never written through; the
+  // blocks above are only read), the blocks wholly above the new length are unreferenced and unmapped
+  // afterwards, and the device tables are uploaded again, the decode rows' included, before the call returns
+  // (the captured decode graphs read them in place).  n_keep + n_discard == n_tokens only truncates.  Decode
+  // rows of the slot are moved back to the new length: the slot's next step must be host-fed (explicit token
+  // and position).  Throws before any table, refcount or cache byte changes on: a bad slot, n_tokens outside
+  // [1, max_ctx], n_keep < 0, n_discard < 1, n_keep + n_discard > n_tokens, a pipelined step in flight
+  // (sampled by decode_sample and not yet collected), an engine that is not finalized or is tensor-parallel,
+  // a pool without the free blocks the un-sharing needs.
+  int shift_context(int slot, int n_tokens, int n_keep, int n_discard);
   int kv_blocks_free() const { return (int)free_blocks_.size(); }
   int kv_blocks_total() const { return kv_nblocks_; }
   int norm_fused_parts() const { return nrm_parts_; }  // 0: batched-decode RMSNorm not split into the GEMMs
@@ -633,6 +645,7 @@ class Engine {
   void kv_copy_block(int src, int dst);
   void kv_prepare_write(int slot, int from, int to);  // map + un-share the blocks of [from, to)
   void kv_sync(int B);                                 // upload dirty tables (rows 0..B-1)
+  float* d_shift_kscale_ = nullptr;                    // [n_layers] the K scales shift_context's launch reads (fp8)
 
   std::map<int, hipGraphExec_t> graphs_;
   AllReduceFn allreduce_ = nullptr;

@@ -2281,6 +2281,60 @@ void Engine::release_slot(int slot) {
   }
 }
 
+int Engine::shift_context(int slot, int n_tokens, int n_keep, int n_discard) {
+  const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  if (cfg_.tp_size > 1) throw std::runtime_error("shift_context: not available on a tensor-parallel engine");
+  if (pipe_sampled_) throw std::runtime_error("shift_context: a pipelined step is in flight");
+  if (slot < 0 || slot >= cfg_.max_slots) throw std::runtime_error("shift_context: bad slot");
+  if (n_tokens < 1 || n_tokens > cfg_.max_ctx) throw std::runtime_error("shift_context: n_tokens out of range");
+  if (n_keep < 0) throw std::runtime_error("shift_context: n_keep is negative");
+  if (n_discard < 1) throw std::runtime_error("shift_context: n_discard below 1");
+  if (n_keep > n_tokens - n_discard) throw std::runtime_error("shift_context: n_keep + n_discard beyond n_tokens");
+  const int n_new = n_tokens - n_discard;
+  int* row = bt_.data() + (size_t)slot * kv_maxb_;
+  {
+    // the blocks kv_prepare_write will take, counted first: a throw half way would leave the tables changed
+    size_t need = 0;
+    if (n_new > n_keep)
+      for (int j = n_keep / KV_BLOCK; j <= (n_new - 1) / KV_BLOCK; ++j) need += row[j] < 0 || refcnt_[row[j]] > 1;
+    if (need > free_blocks_.size()) throw std::runtime_error("paged KV: pool exhausted");
+  }
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  TraceRange tr("aios.shift_context");
+  kv_prepare_write(slot, n_keep, n_new);
+  kv_sync(0);
+  if (n_new > n_keep) {
+    KvShiftArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.k_cache = k_cache_; a.v_cache = v_cache_; a.layer_elems = layer_kv_elems_;
+    a.block_table = d_bt_; a.max_blocks = kv_maxb_; a.slot = slot;
+    a.n_layers = cfg_.n_layers; a.n_kv_heads = cfg_.n_kv_heads; a.head_dim = cfg_.head_dim;
+    a.n_tokens = n_tokens; a.n_keep = n_keep; a.n_discard = n_discard;
+    a.rope_cs = rope_cs_; a.rope_rows = cfg_.max_ctx; a.rope_neox = cfg_.rope_neox; a.kv_fp8 = cfg_.kv_fp8;
+    if (cfg_.kv_fp8) {
+      if (!d_shift_kscale_) d_shift_kscale_ = (float*)dmalloc((size_t)cfg_.n_layers * 4);
+      std::vector<float> ks(cfg_.n_layers);
+      for (int l = 0; l < cfg_.n_layers; ++l) ks[l] = kv_scale_[2 * l];
+      HIP_CHECK(hipMemcpyAsync(d_shift_kscale_, ks.data(), ks.size() * 4, hipMemcpyHostToDevice, stream_));
+      HIP_CHECK(hipStreamSynchronize(stream_));  // (ks is pageable and leaves scope)
+      a.k_scale = d_shift_kscale_;
+    }
+    launch_kv_shift(a, stream_);
+  }
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  for (int j = (n_new + KV_BLOCK - 1) / KV_BLOCK; j < kv_maxb_; ++j) {
+    kv_unref(row[j]);
+    row[j] = -1;
+  }
+  // decode rows of the slot: their host positions are not beyond the new length (advance_rows maps from there)
+  for (size_t b = 0; b < row_slots_.size(); ++b)
+    if (row_slots_[b] == slot) row_pos_[b] = std::min(row_pos_[b], n_new);
+  bt_dirty_ = true;
+  kv_sync((int)std::min(row_slots_.size(), (size_t)cfg_.max_batch));
+  return n_new;
+}
+
 std::vector<int> Engine::block_table(int slot) const {
   if (slot < 0 || slot >= cfg_.max_slots) throw std::runtime_error("block_table: bad slot");
   return std::vector<int>(bt_.begin() + (size_t)slot * kv_maxb_, bt_.begin() + (size_t)(slot + 1) * kv_maxb_);

@@ -333,6 +333,34 @@ struct EmbedPoolArgs {
 void launch_embed_pool(const EmbedPoolArgs& a, hipStream_t st);
 size_t embed_pool_ws_bytes(int d);
 
+// ---- context shift -----------------------------------------------------------------------------
+// A slot holds positions [0, n_tokens).  Positions [0, n_keep) stay, [n_keep, n_keep + n_discard) are
+// forgotten, every position p at or above n_keep + n_discard becomes p - n_discard (llama.cpp's context
+// shift; the new length is n_tokens - n_discard).  A moved V row is the same bytes.  A moved K row is the
+// stored (RoPE'd) row rotated by -n_discard positions: pair i with stored (x, y) and (c, s) = rope_cs
+// [n_discard][i] becomes (x c + y s, -x s + y c) in fp32, rounded to the cache type (bf16 nearest-even; fp8:
+// decoded with the layer's K scale and re-encoded with it by the KV writers' conversion).  Pairs are
+// (2i, 2i + 1), or (i, i + head_dim / 2) when rope_neox.  In place, through row `slot` of the block table:
+// every block of the destination range must be mapped and private, every block of the source range mapped
+// (Engine::shift_context).  n_keep + n_discard == n_tokens moves nothing.  One launch for every layer;
+// kernels/kv_shift.hip, tests/context_shift_oracle.py is this rule in float64.
+struct KvShiftArgs {
+  bf16_t* k_cache;         // layer 0's pools (element indices as bf16, bytes when kv_fp8)
+  bf16_t* v_cache;
+  size_t layer_elems;      // elements from one layer's pool to the next
+  const int* block_table;  // [slots][max_blocks], unmapped entries: the null block
+  int max_blocks;
+  int slot;
+  int n_layers, n_kv_heads, head_dim;
+  int n_tokens, n_keep, n_discard;
+  const float2* rope_cs;   // [rope_rows][head_dim / 2] (cos, sin)
+  int rope_rows;
+  int rope_neox;
+  int kv_fp8;
+  const float* k_scale;    // [n_layers] on the device (fp8 only): value = code * scale
+};
+void launch_kv_shift(const KvShiftArgs& a, hipStream_t st);
+
 // ---- MFMA GEMM (prefill) ----------------------------------------------------------------------
 // C[M][N] (fp32, epilogue) = A[M][K] (bf16) x W[N][K]^T (quantized, dequantized tile-wise in LDS)
 struct GemmArgs {

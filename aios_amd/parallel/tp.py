@@ -519,6 +519,16 @@ def spec_speculative(path: str) -> dict:
     return out
 
 
+def spec_context_shift(path: str) -> bool:
+    """the '#...&ctxshift=1' fragment of a model spec: the tier's context-shift default (Scheduler's
+    `context_shift`); off when absent"""
+    for kv in filter(None, path.partition("#")[2].split("&")):
+        k, _, v = kv.partition("=")
+        if k == "ctxshift":
+            return v not in ("0", "false", "no", "off")
+    return False
+
+
 def parse_spec(path: str):
     """'synthetic:<preset>[:<recipe>]#tp=N&q8=0' or '<file.gguf>#tp=N' -> (base, tp, act_q8).
     q8=0 selects fp32 activations in the GEMVs (int8 activations are the default); kv=fp8_e4m3 the

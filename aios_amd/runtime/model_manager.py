@@ -188,7 +188,7 @@ class ModelManager:
 
         E = native.require()
         from ..parallel.tp import (launch_tp, parse_spec, spec_kv_calibrate, spec_kv_dtype, spec_sampling,
-                                   spec_speculative)
+                                   spec_context_shift, spec_speculative)
 
         device = self.device if m.device < 0 else m.device
 
@@ -257,7 +257,7 @@ class ModelManager:
         batch = getattr(eng.config, "max_batch", self.max_batch)
         m.scheduler = Scheduler(eng, tok, min(batch, self.max_batch), min(slots, self.max_slots), m.context_length,
                                 m.grammar, name=m.name, sampling_defaults=spec_sampling(m.path),
-                                speculative=spec_speculative(m.path))
+                                speculative=spec_speculative(m.path), context_shift=spec_context_shift(m.path))
         # capture every batch size's decode-step graph now, not on the first step that reaches it
         # (a capture stalls that step by milliseconds; AIOS_GRAPH_WARMUP=0 skips)
         capture = getattr(eng, "capture_graphs", None)

@@ -97,6 +97,14 @@ class GenRequest:
     # the output (OpenAI's Predicted Outputs), searched for drafts before the prompt itself
     speculative: Optional[bool] = None
     prediction_ids: Optional[List[int]] = None
+    # context shift (llama-server's n_keep / context shift; the engine's shift_context): when the slot reaches the
+    # context window and max_tokens is not, the oldest part of the conversation behind the first n_keep prompt
+    # tokens is dropped -- n_discard = (n_past - n_keep) // 2 tokens, llama.cpp's numbers -- the rest moves down
+    # with its keys re-rotated, and generation goes on; max_tokens is then not clamped to the window.  n_keep:
+    # -1 = the whole prompt; any value is clamped to the prompt length.  The tier's default (node config
+    # context_shift) applies to requests that leave the flag off
+    context_shift: bool = False
+    n_keep: int = -1
     stop_ids: Optional[List[int]] = None
     on_delta: Optional[Callable[[str], None]] = None
     on_done: Optional[Callable[["GenResult"], None]] = None
@@ -129,6 +137,7 @@ class GenResult:
     # accepted (both 0 when nothing was drafted)
     draft_tokens: int = 0
     accepted_draft_tokens: int = 0
+    context_shifts: int = 0           # context shifts the request went through
 
 
 # the tier's speculative-decoding settings (node config: speculative, spec_draft_max, spec_ngram_min / _max,
@@ -139,7 +148,7 @@ SPEC_DEFAULTS = dict(mode="off", draft_max=7, ngram_min=2, ngram_max=3, max_cont
 class _Seq:
     __slots__ = ("req", "slot", "pos", "last", "out", "grammar_state", "emitted", "t_first", "cached", "todo",
                  "p_off", "r_off", "seed", "proc", "pen_n", "bias", "bias_soft", "lp_n", "lps", "embedding", "plp_n", "plps",
-                 "spec", "drafter", "drafted", "draft_hits")
+                 "spec", "drafter", "drafted", "draft_hits", "shift", "n_keep", "shifts")
 
     def __init__(self, req, slot):
         self.req, self.slot = req, slot
@@ -167,6 +176,9 @@ class _Seq:
         self.drafter = None          # its LookupDrafter over prompt + out, built when decoding starts
         self.drafted = 0             # draft tokens verified / accepted so far
         self.draft_hits = 0
+        self.shift = False           # context shift on for this request (set at admission)
+        self.n_keep = 0              # its n_keep, clamped to the prompt
+        self.shifts = 0              # shifts so far; from the first on the slot's cached tokens stay cut to n_keep
         self.p_off = 0              # incremental detokenization window [p_off, r_off) already emitted
         self.r_off = 0
 
@@ -174,8 +186,13 @@ class _Seq:
 class Scheduler:
     def __init__(self, engine, tokenizer, max_batch: int, max_slots: int, max_ctx: int, grammar=None,
                  name: str = "model", sampling_defaults: Optional[Dict[str, float]] = None,
-                 speculative: Optional[dict] = None):
+                 speculative: Optional[dict] = None, context_shift: bool = False):
         self.engine = engine
+        # context shift (GenRequest.context_shift; this is the tier's default for requests that leave it off); it
+        # needs the engine's shift_context, which the CPU and tensor-parallel tiers lack
+        self.context_shift = bool(context_shift)
+        self.can_shift = hasattr(engine, "shift_context")
+        self._warned_no_shift = False
         # speculative decoding (SPEC_DEFAULTS; off unless the tier or a request turns it on); it needs the
         # engine's spec_decode, which the CPU and tensor-parallel tiers lack: they decode plainly and say so once
         self.spec = dict(SPEC_DEFAULTS)
@@ -233,7 +250,7 @@ class Scheduler:
         self.stop_flag = False
         self.stats = dict(requests=0, tokens=0, prefill_tokens=0, cached_tokens=0, steps=0, batch_sum=0, errors=0,
                           embeddings=0, prompt_scores=0, spec_steps=0, spec_drafted=0, spec_accepted=0,
-                          bias_overridden=0)
+                          bias_overridden=0, context_shifts=0, shifted_tokens=0)
         # health / metrics (ModelManager.supervise and HealthCheck details)
         self.max_slots = max_slots
         self.last_progress = time.time()   # last completed admission or decode step
@@ -417,7 +434,16 @@ class Scheduler:
             if not self.can_logprobs:
                 raise ValueError(f"{self.name}: this tier's engine cannot report logprobs")
         bias = self._bias_of(r)
-        r.max_tokens = max(0 if score else 1, min(r.max_tokens, self.max_ctx - len(ids)))
+        shift = bool(r.context_shift)
+        if shift and not self.can_shift:
+            raise ValueError(f"{self.name}: context_shift: single-GPU engines only")
+        if not shift and self.context_shift:  # the tier's default
+            shift = self.can_shift
+            if not shift and not self._warned_no_shift:
+                self._warned_no_shift = True
+                log.warning("%s: the engine has no shift_context; context shift is off on this tier", self.name)
+        # (a request that shifts is not bounded by the window)
+        r.max_tokens = max(0 if score else 1, r.max_tokens if shift else min(r.max_tokens, self.max_ctx - len(ids)))
         r.min_tokens = min(r.min_tokens, r.max_tokens)
         if score:  # cached positions have no logits to score: from position 0, in the least useful slot
             slot, common = min(self.free_slots, key=lambda f: len(self.slot_cache[f])), 0
@@ -425,6 +451,8 @@ class Scheduler:
             slot, common = self._pick_slot(ids)
         self.free_slots.remove(slot)
         seq = _Seq(r, slot)
+        seq.shift = shift
+        seq.n_keep = len(ids) if int(r.n_keep) < 0 else min(int(r.n_keep), len(ids))
         if score:
             seq.plp_n = int(r.prompt_logprobs)
         d = self.sampling_defaults
@@ -606,13 +634,43 @@ class Scheduler:
         if seq.grammar_state is not None and self.grammar.complete(seq.grammar_state):
             self._finish(seq, "grammar")
             return False
-        if len(seq.out) >= r.max_tokens or seq.pos + 1 >= self.max_ctx:
+        if len(seq.out) >= r.max_tokens or (seq.pos + 1 >= self.max_ctx and not (seq.shift and self._shift(seq))):
             self._finish(seq, "length")
             return False
         if r.deadline and time.time() > r.deadline:
             self._finish(seq, "deadline")
             return False
         return True
+
+    def _shift(self, seq: _Seq) -> bool:
+        """The slot reached the window: drop n_discard = (n_past - n_keep) // 2 tokens behind the first n_keep
+        (llama.cpp's numbers) through the engine's shift_context and go on at the new position; the next step of
+        the row is host-fed (no forward of it is queued: _can_speculate refuses a row this close to the window).
+        False: nothing can be dropped, or the pool has no block for the un-sharing -- the request ends "length"."""
+        self._drain()  # (no other engine call while a pipelined step is in flight)
+        n_past = seq.pos
+        n_discard = (n_past - seq.n_keep) // 2
+        if n_discard < 1:
+            return False
+        try:
+            seq.pos = int(self.engine.shift_context(seq.slot, n_past, seq.n_keep, n_discard))
+        except RuntimeError as e:
+            if "pool exhausted" not in str(e):
+                raise
+            return False
+        # the moved keys are not what a prefill of those tokens would write: never inherited as a prefix
+        seq.shifts += 1
+        del self.slot_cache[seq.slot][seq.n_keep:]
+        self.stats["context_shifts"] += 1
+        self.stats["shifted_tokens"] += n_past - seq.n_keep - n_discard
+        return True
+
+    def _advance(self, s: _Seq):
+        """The row's token went in at s.pos: the position moves on, and so does the slot's record of cached tokens
+        (until the first context shift: behind it the slot no longer holds what a prefill would write)."""
+        s.pos += 1
+        if not s.shifts:
+            self.slot_cache[s.slot].append(s.last)
 
     def _engine_failed(self, e: BaseException):
         self.stats["errors"] += 1
@@ -675,8 +733,7 @@ class Scheduler:
         self.stats["batch_sum"] += len(rows)
         lps = self._read_logprobs(rows)
         for s, t, lp in zip(rows, out, lps):
-            s.pos += 1
-            self.slot_cache[s.slot].append(s.last)
+            self._advance(s)
             self._accept(s, int(t), lp)
 
     def _can_speculate(self, rows) -> bool:
@@ -877,8 +934,7 @@ class Scheduler:
         s.draft_hits += int(acc)
         lps = self._read_logprobs(rows)
         for i, t in enumerate(out):  # stops at the first token that finishes the request: the rest is dropped
-            s.pos += 1
-            self.slot_cache[s.slot].append(s.last)
+            self._advance(s)
             if not self._accept(s, int(t), lps[i]):
                 break
         t3 = time.perf_counter()
@@ -920,8 +976,7 @@ class Scheduler:
         self.stats["batch_sum"] += B
         lps = self._read_logprobs(rows)
         for s, t, lp in zip(rows, out, lps):
-            s.pos += 1
-            self.slot_cache[s.slot].append(s.last)
+            self._advance(s)
             self._accept(s, int(t), lp)
         t3 = time.perf_counter()
         tm = self.timing
@@ -949,7 +1004,7 @@ class Scheduler:
             latency_ms=(now - r.submitted_at) * 1e3, cached_prompt_tokens=seq.cached, error=error,
             logprobs=list(seq.lps) if seq.lp_n >= 0 else None, embedding=seq.embedding,
             prompt_logprobs=list(seq.plps) if seq.plp_n >= 0 else None,
-            draft_tokens=seq.drafted, accepted_draft_tokens=seq.draft_hits))
+            draft_tokens=seq.drafted, accepted_draft_tokens=seq.draft_hits, context_shifts=seq.shifts))
 
     @staticmethod
     def _done(r: GenRequest, res: GenResult):

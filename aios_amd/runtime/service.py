@@ -137,6 +137,22 @@ def bias_from_body(body: dict, scheduler):
     return (bias or None), bool(ieos)
 
 
+def shift_from_body(body: dict, scheduler):
+    """`context_shift` (a boolean) and `n_keep` (an integer >= -1; -1: the whole prompt) of a chat or completions
+    body, llama-server's fields: (GenRequest.context_shift, GenRequest.n_keep, whether usage reports
+    context_shifts -- the body names one of the fields or the tier shifts by default).  ValueError (-> 400) for a
+    malformed field and on a tier whose engine cannot shift (a tensor-parallel or CPU tier)."""
+    flag, keep = body.get("context_shift"), body.get("n_keep")
+    if flag is not None and not isinstance(flag, bool):
+        raise ValueError("context_shift must be a boolean")
+    if keep is not None and (isinstance(keep, bool) or not isinstance(keep, int) or keep < -1):
+        raise ValueError("n_keep must be an integer >= -1")
+    if flag and not getattr(scheduler, "can_shift", False):
+        raise ValueError("context_shift: single-GPU engines only")
+    named = "context_shift" in body or "n_keep" in body
+    return bool(flag), -1 if keep is None else int(keep), named or bool(getattr(scheduler, "context_shift", False))
+
+
 def prediction_from_body(body: dict, tokenizer):
     """`prediction` (OpenAI's Predicted Outputs) and `speculative` (a boolean, an extension) of a chat or
     completions body: (GenRequest.speculative, GenRequest.prediction_ids).  A prediction turns prompt-lookup
@@ -281,7 +297,9 @@ def completion_request(body: dict, tokenizer, scheduler) -> dict:
         raise ValueError(f"bad sampling field: {e}") from None
     speculative, prediction_ids = prediction_from_body(body, tokenizer)
     logit_bias, ignore_eos = bias_from_body(body, scheduler)
-    return dict(logit_bias=logit_bias, ignore_eos=ignore_eos, ids=ids, prompt_text=text, max_tokens=int(max_tokens), temperature=max(temperature, 0.0),
+    context_shift, n_keep, shift_usage = shift_from_body(body, scheduler)
+    return dict(context_shift=context_shift, n_keep=n_keep, shift_usage=shift_usage,
+                logit_bias=logit_bias, ignore_eos=ignore_eos, ids=ids, prompt_text=text, max_tokens=int(max_tokens), temperature=max(temperature, 0.0),
                 echo=bool(echo), logprobs=lp, stream=stream, sampling=sampling, repeat_last_n=rln,
                 speculative=speculative, prediction_ids=prediction_ids)
 
@@ -341,6 +359,7 @@ async def complete(m, c: dict, on_delta=None, timeout: float = 120.0) -> GenResu
             req.prompt_logprobs = int(c["logprobs"])
     req.speculative, req.prediction_ids = c.get("speculative"), c.get("prediction_ids")
     req.logit_bias, req.ignore_eos = c.get("logit_bias"), bool(c.get("ignore_eos"))
+    req.context_shift, req.n_keep = bool(c.get("context_shift")), int(c.get("n_keep", -1))
     m.scheduler.submit(req)
     try:
         return await asyncio.wait_for(fut, timeout + 5)
@@ -373,11 +392,11 @@ async def generate(m, messages, max_tokens: int, temperature: float, json_mode: 
                    timeout: float = 120.0, seed: int = 0, sampling: Optional[dict] = None,
                    top_logprobs: Optional[int] = None, speculative: Optional[bool] = None,
                    prediction_ids: Optional[List[int]] = None, logit_bias: Optional[Dict[int, float]] = None,
-                   ignore_eos: bool = False) -> GenResult:
+                   ignore_eos: bool = False, context_shift: bool = False, n_keep: int = -1) -> GenResult:
     """sampling: further GenRequest fields by name (top_p, top_k, seed, min_p, the penalties);
     top_logprobs: None, or per-token logprobs with that many alternatives (GenResult.logprobs);
     speculative / prediction_ids: GenRequest's (prediction_from_body); logit_bias / ignore_eos:
-    GenRequest's (bias_from_body)"""
+    GenRequest's (bias_from_body); context_shift / n_keep: GenRequest's (shift_from_body)"""
     loop = asyncio.get_running_loop()
     fut = loop.create_future()
     prompt = m.template.render(messages, add_generation_prompt=True)
@@ -400,6 +419,7 @@ async def generate(m, messages, max_tokens: int, temperature: float, json_mode: 
         req.logprobs, req.top_logprobs = True, int(top_logprobs)
     req.speculative, req.prediction_ids = speculative, prediction_ids
     req.logit_bias, req.ignore_eos = logit_bias, ignore_eos
+    req.context_shift, req.n_keep = context_shift, n_keep
     m.scheduler.submit(req)
     try:
         return await asyncio.wait_for(fut, timeout + 5)
@@ -577,6 +597,7 @@ class AIRuntimeService:
             top_logprobs = logprobs_from_body(body, m.scheduler)
             speculative, prediction_ids = prediction_from_body(body, m.tokenizer)
             logit_bias, ignore_eos = bias_from_body(body, m.scheduler)
+            context_shift, n_keep, shift_usage = shift_from_body(body, m.scheduler)
         except ValueError as e:
             return web.json_response({"error": {"message": str(e), "type": "invalid_request_error"}}, status=400)
         created = int(time.time())
@@ -588,7 +609,7 @@ class AIRuntimeService:
             task = asyncio.ensure_future(generate(m, messages, max_tokens, temperature, json_mode, on_delta=q.put_nowait,
                                                   sampling=sampling, speculative=speculative,
                                                   prediction_ids=prediction_ids, logit_bias=logit_bias,
-                                                  ignore_eos=ignore_eos))
+                                                  ignore_eos=ignore_eos, context_shift=context_shift, n_keep=n_keep))
             task.add_done_callback(lambda _t: q.put_nowait(None))
             while True:
                 d = await q.get()
@@ -605,17 +626,20 @@ class AIRuntimeService:
             return resp
         res = await generate(m, messages, max_tokens, temperature, json_mode, sampling=sampling,
                              top_logprobs=top_logprobs, speculative=speculative, prediction_ids=prediction_ids,
-                             logit_bias=logit_bias, ignore_eos=ignore_eos)
+                             logit_bias=logit_bias, ignore_eos=ignore_eos, context_shift=context_shift, n_keep=n_keep)
         choice = {"index": 0, "message": {"role": "assistant", "content": res.text},
                   "finish_reason": "length" if res.finish_reason == "length" else "stop"}
         if top_logprobs is not None:  # (bodies of requests that did not ask stay as they were)
             choice["logprobs"] = {"content": logprobs_content(m.tokenizer, res.logprobs)}
+        usage = {"prompt_tokens": res.prompt_tokens, "completion_tokens": res.completion_tokens,
+                 "total_tokens": res.prompt_tokens + res.completion_tokens,
+                 "completion_tokens_details": prediction_usage(res)}
+        if shift_usage:  # (a body that names neither field on a tier that does not shift stays as it was)
+            usage["context_shifts"] = int(res.context_shifts)
         return web.json_response({
             "id": rid, "object": "chat.completion", "created": created, "model": m.name,
             "choices": [choice],
-            "usage": {"prompt_tokens": res.prompt_tokens, "completion_tokens": res.completion_tokens,
-                      "total_tokens": res.prompt_tokens + res.completion_tokens,
-                      "completion_tokens_details": prediction_usage(res)},
+            "usage": usage,
             "timings": {"ttft_ms": res.ttft_ms, "latency_ms": res.latency_ms,
                         "cached_prompt_tokens": res.cached_prompt_tokens},
         })
@@ -680,6 +704,8 @@ class AIRuntimeService:
         # (the usage of a body that names neither field on a tier that does not speculate stays as it was)
         if c["speculative"] is not None or getattr(m.scheduler, "spec", {}).get("mode", "off") != "off":
             usage["completion_tokens_details"] = prediction_usage(res)
+        if c["shift_usage"]:  # (likewise)
+            usage["context_shifts"] = int(res.context_shifts)
         return web.json_response({
             "id": rid, "object": "text_completion", "created": created, "model": m.name, "choices": [choice],
             "usage": usage,

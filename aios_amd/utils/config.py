@@ -61,6 +61,9 @@ class ModelTier:
     spec_ngram_min: int = 2
     spec_ngram_max: int = 3
     spec_max_context: int = 4096
+    # context shift by default for the tier's requests (runtime/scheduler.py: GenRequest.context_shift): at the
+    # context window the oldest tokens behind the prompt are dropped and generation goes on; single-GPU tiers
+    context_shift: bool = False
 
     def speculative_frag(self) -> List[str]:
         """the non-default speculative settings as model-spec fragments (parallel.tp.spec_speculative)"""
@@ -172,6 +175,8 @@ class NodeConfig:
                     frag.append(f"kvcal={t.kv_calibrate}")
             frag += t.sampling_frag()
             frag += t.speculative_frag()
+            if t.context_shift:
+                frag.append("ctxshift=1")
             devs = list(t.devices)
             if not devs and t.replicas > 1:
                 devs = list(self.models.devices[:t.replicas]) or list(range(t.replicas))
@@ -212,6 +217,8 @@ class NodeConfig:
                     frag.append(f"kvcal={t.kv_calibrate}")
             frag += t.sampling_frag()
             frag += t.speculative_frag()
+            if t.context_shift:
+                frag.append("ctxshift=1")
             out.append((name, path + ("#" + "&".join(frag) if frag else ""), t.context_length))
         return out
 
