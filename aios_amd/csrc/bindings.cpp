@@ -379,6 +379,34 @@ PYBIND11_MODULE(_engine, m) {
       .def("release_slot", &Engine::release_slot)
       .def("shift_context", &Engine::shift_context, py::call_guard<py::gil_scoped_release>(), py::arg("slot"),
            py::arg("n_tokens"), py::arg("n_keep"), py::arg("n_discard"))
+      .def("kv_snapshot_bytes", &Engine::kv_snapshot_bytes, py::arg("n_tokens"))
+      .def("kv_save",
+           [](Engine& e, int slot, int n_tokens) {
+             // the snapshot payload of a slot's first n_tokens positions, kv_read's bytes (written straight into
+             // the bytes object: no second copy of the slot on the host either)
+             // (an n_tokens out of range: no allocation by it, the engine's refusal instead)
+             const size_t n = n_tokens <= e.config().max_ctx ? e.kv_snapshot_bytes(n_tokens) : 0;
+             PyObject* o = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)n);
+             if (!o) throw py::error_already_set();
+             py::bytes out = py::reinterpret_steal<py::bytes>(o);
+             char* p = PyBytes_AS_STRING(o);
+             {
+               py::gil_scoped_release nogil;
+               e.kv_save(slot, n_tokens, p, n);
+             }
+             return out;
+           },
+           py::arg("slot"), py::arg("n_tokens"))
+      .def("kv_restore",
+           [](Engine& e, int slot, py::buffer data, int n_tokens) {
+             py::buffer_info bi = data.request();
+             const size_t n = (size_t)bi.size * bi.itemsize;
+             if (bi.ndim > 1 || (bi.ndim == 1 && bi.strides[0] != bi.itemsize))
+               throw std::runtime_error("kv_restore: data must be contiguous");
+             py::gil_scoped_release nogil;
+             e.kv_restore(slot, bi.ptr, n, n_tokens);
+           },
+           py::arg("slot"), py::arg("data"), py::arg("n_tokens"))
       .def("block_table", &Engine::block_table)
       .def("kv_read",
            [](const Engine& e, int slot, int n_tokens) {
@@ -899,6 +927,24 @@ PYBIND11_MODULE(_engine, m) {
         },
         py::arg("in_tokens"), py::arg("out_tokens"), py::arg("pos0"), py::arg("R"), py::arg("record"), py::arg("tokens"),
         py::arg("pos"), py::arg("seq_len"), py::arg("history"), py::arg("hist_stride"), py::arg("st"));
+  m.def("kv_snapshot",
+        [](uintptr_t k_cache, uintptr_t v_cache, size_t layer_bytes, uintptr_t buf, uintptr_t block_table, int max_blocks,
+           int n_blocks, int slot, int n_tokens, int n_layers, int n_kv_heads, int head_dim, int elem_bytes, bool unpack,
+           int layer0, uintptr_t st) {
+          // k_cache / v_cache: [layer] pools of layer_bytes each, [n_blocks + 1][n_kv_heads][KV_BLOCK][head_dim];
+          // buf: [n_layers][2][n_kv_heads][n_tokens][head_dim]; block_table: [slots][max_blocks] ints
+          KvSnapArgs a;
+          std::memset(&a, 0, sizeof(a));
+          a.k_cache = (void*)k_cache; a.v_cache = (void*)v_cache; a.layer_bytes = layer_bytes; a.buf = (void*)buf;
+          a.block_table = (const int*)block_table; a.max_blocks = max_blocks; a.n_blocks = n_blocks; a.slot = slot;
+          a.layer0 = layer0; a.n_layers = n_layers; a.n_kv_heads = n_kv_heads; a.head_dim = head_dim;
+          a.n_tokens = n_tokens; a.elem_bytes = elem_bytes; a.unpack = unpack ? 1 : 0;
+          launch_kv_snapshot(a, S(st));
+        },
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("layer_bytes"), py::arg("buf"), py::arg("block_table"),
+        py::arg("max_blocks"), py::arg("n_blocks"), py::arg("slot"), py::arg("n_tokens"), py::arg("n_layers"),
+        py::arg("n_kv_heads"), py::arg("head_dim"), py::arg("elem_bytes"), py::arg("unpack"), py::arg("layer0") = 0,
+        py::arg("st") = 0);
   m.attr("EMBED_NONE") = (int)EMBED_NONE;
   m.attr("EMBED_MEAN") = (int)EMBED_MEAN;
   m.attr("EMBED_LAST") = (int)EMBED_LAST;

@@ -302,6 +302,20 @@ class Engine {
   // (sampled by decode_sample and not yet collected), an engine that is not finalized or is tensor-parallel,
   // a pool without the free blocks the un-sharing needs.
   int shift_context(int slot, int n_tokens, int n_keep, int n_discard);
+  // KV snapshots (ops.h KvSnapArgs: the payload).  kv_snapshot_bytes: the exact payload size of n_tokens
+  // positions.  kv_save: the slot's positions [0, n_tokens) into out, byte for byte what kv_read returns, one
+  // pack launch and one device-to-host copy per layer.  Staging is bounded: one layer's K and V on the device and
+  // two pinned host buffers of that size, grown on demand and kept; never a second copy of the slot.
+  // kv_restore: the blocks of [0, n_tokens) are mapped and un-shared first (a shared prefix block is never
+  // written through), the slot's blocks above ceil(n_tokens / KV_BLOCK) are unreferenced and unmapped, the data
+  // is unpacked layer by layer and the device tables are uploaded again, the decode rows' included (the captured
+  // decode graphs read them in place).  Decode rows of the slot are moved back to n_tokens: the slot's next step
+  // must be host-fed.  Both throw before any table, refcount or cache byte changes on: a bad slot, n_tokens
+  // outside [1, max_ctx], a size other than kv_snapshot_bytes(n_tokens), a pipelined step in flight, an engine
+  // that is not finalized or is tensor-parallel, (restore) a pool without the free blocks the mapping needs.
+  size_t kv_snapshot_bytes(int n_tokens) const;
+  void kv_save(int slot, int n_tokens, void* out, size_t out_bytes);
+  void kv_restore(int slot, const void* data, size_t data_bytes, int n_tokens);
   int kv_blocks_free() const { return (int)free_blocks_.size(); }
   int kv_blocks_total() const { return kv_nblocks_; }
   int norm_fused_parts() const { return nrm_parts_; }  // 0: batched-decode RMSNorm not split into the GEMMs
@@ -646,6 +660,14 @@ class Engine {
   void kv_prepare_write(int slot, int from, int to);  // map + un-share the blocks of [from, to)
   void kv_sync(int B);                                 // upload dirty tables (rows 0..B-1)
   float* d_shift_kscale_ = nullptr;                    // [n_layers] the K scales shift_context's launch reads (fp8)
+  // kv_save / kv_restore staging: one layer's K and V on the device, two pinned host buffers of that size
+  void* snap_dev_ = nullptr;
+  void* snap_host_[2] = {nullptr, nullptr};
+  hipEvent_t snap_ev_[2] = {nullptr, nullptr};
+  size_t snap_cap_ = 0;
+  void snap_check(const char* who, int slot, int n_tokens, size_t bytes) const;
+  void snap_reserve(size_t layer_bytes);
+  void snap_launch(int slot, int layer, int n_tokens, bool unpack);
 
   std::map<int, hipGraphExec_t> graphs_;
   AllReduceFn allreduce_ = nullptr;

@@ -107,6 +107,11 @@ Engine::~Engine() {
   if (h_proc_) hipHostFree(h_proc_);
   if (h_lp_) hipHostFree(h_lp_);
   if (h_spec_) hipHostFree(h_spec_);
+  if (snap_dev_) hipFree(snap_dev_);
+  for (void* h : snap_host_)
+    if (h) hipHostFree(h);
+  for (hipEvent_t e : snap_ev_)
+    if (e) hipEventDestroy(e);
   if (pipe_ev_) hipEventDestroy(pipe_ev_);
   if (stream_) hipStreamDestroy(stream_);
 }
@@ -2333,6 +2338,112 @@ int Engine::shift_context(int slot, int n_tokens, int n_keep, int n_discard) {
   bt_dirty_ = true;
   kv_sync((int)std::min(row_slots_.size(), (size_t)cfg_.max_batch));
   return n_new;
+}
+
+// ---- KV snapshots ------------------------------------------------------------------------------
+size_t Engine::kv_snapshot_bytes(int n_tokens) const {
+  return (size_t)cfg_.n_layers * 2 * cfg_.n_kv_heads * (size_t)std::max(n_tokens, 0) * cfg_.head_dim * kv_es_;
+}
+
+void Engine::snap_check(const char* who, int slot, int n_tokens, size_t bytes) const {
+  const std::string w(who);
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  if (cfg_.tp_size > 1) throw std::runtime_error(w + ": not available on a tensor-parallel engine");
+  if (pipe_sampled_) throw std::runtime_error(w + ": a pipelined step is in flight");
+  if (slot < 0 || slot >= cfg_.max_slots) throw std::runtime_error(w + ": bad slot");
+  if (n_tokens < 1 || n_tokens > cfg_.max_ctx) throw std::runtime_error(w + ": n_tokens out of range");
+  if (bytes != kv_snapshot_bytes(n_tokens))
+    throw std::runtime_error(w + ": payload of " + std::to_string(bytes) + " bytes, " + std::to_string(n_tokens) +
+                             " tokens are " + std::to_string(kv_snapshot_bytes(n_tokens)));
+}
+
+void Engine::snap_reserve(size_t layer_bytes) {
+  for (auto& e : snap_ev_)
+    if (!e) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (layer_bytes <= snap_cap_) return;
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  if (snap_dev_) HIP_CHECK(hipFree(snap_dev_));
+  snap_dev_ = nullptr;
+  for (auto& h : snap_host_) {
+    if (h) HIP_CHECK(hipHostFree(h));
+    h = nullptr;
+  }
+  snap_cap_ = 0;
+  HIP_CHECK(hipMalloc(&snap_dev_, layer_bytes));
+  for (auto& h : snap_host_) HIP_CHECK(hipHostMalloc(&h, layer_bytes, hipHostMallocDefault));
+  snap_cap_ = layer_bytes;
+}
+
+void Engine::snap_launch(int slot, int layer, int n_tokens, bool unpack) {
+  KvSnapArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.k_cache = k_cache_; a.v_cache = v_cache_; a.layer_bytes = layer_kv_elems_ * kv_es_;
+  a.buf = snap_dev_; a.block_table = d_bt_; a.max_blocks = kv_maxb_; a.n_blocks = kv_nblocks_; a.slot = slot;
+  a.layer0 = layer; a.n_layers = 1; a.n_kv_heads = cfg_.n_kv_heads; a.head_dim = cfg_.head_dim;
+  a.n_tokens = n_tokens; a.elem_bytes = kv_es_; a.unpack = unpack ? 1 : 0;
+  launch_kv_snapshot(a, stream_);
+}
+
+void Engine::kv_save(int slot, int n_tokens, void* out, size_t out_bytes) {
+  const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
+  snap_check("kv_save", slot, n_tokens, out_bytes);
+  if (!out) throw std::runtime_error("kv_save: null buffer");
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  TraceRange tr("aios.kv_save");
+  const size_t lb = out_bytes / cfg_.n_layers;  // one layer's K and V
+  snap_reserve(lb);
+  kv_sync(0);  // (the device table is the host's)
+  // layer l: pack into the device staging, copy to pinned buffer l % 2; the host copies layer l - 1 out of the
+  // other pinned buffer meanwhile.  The stream orders the staging's reuse; the host's own order a pinned buffer's.
+  auto drain = [&](int l) {
+    HIP_CHECK(hipEventSynchronize(snap_ev_[l & 1]));
+    std::memcpy((char*)out + (size_t)l * lb, snap_host_[l & 1], lb);
+  };
+  for (int l = 0; l < cfg_.n_layers; ++l) {
+    snap_launch(slot, l, n_tokens, false);
+    HIP_CHECK(hipMemcpyAsync(snap_host_[l & 1], snap_dev_, lb, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipEventRecord(snap_ev_[l & 1], stream_));
+    if (l > 0) drain(l - 1);
+  }
+  drain(cfg_.n_layers - 1);
+}
+
+void Engine::kv_restore(int slot, const void* data, size_t data_bytes, int n_tokens) {
+  const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
+  snap_check("kv_restore", slot, n_tokens, data_bytes);
+  if (!data) throw std::runtime_error("kv_restore: null buffer");
+  int* row = bt_.data() + (size_t)slot * kv_maxb_;
+  const int nb = (n_tokens + KV_BLOCK - 1) / KV_BLOCK;
+  {
+    // the blocks kv_prepare_write will take, counted first: a throw half way would leave the tables changed
+    size_t need = 0;
+    for (int j = 0; j < nb; ++j) need += row[j] < 0 || refcnt_[row[j]] > 1;
+    if (need > free_blocks_.size()) throw std::runtime_error("paged KV: pool exhausted");
+  }
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  TraceRange tr("aios.kv_restore");
+  const size_t lb = data_bytes / cfg_.n_layers;
+  snap_reserve(lb);  // (may throw: nothing has changed yet)
+  kv_prepare_write(slot, 0, n_tokens);
+  for (int j = nb; j < kv_maxb_; ++j) {
+    kv_unref(row[j]);
+    row[j] = -1;
+  }
+  bt_dirty_ = true;
+  kv_sync(0);
+  for (int l = 0; l < cfg_.n_layers; ++l) {
+    if (l >= 2) HIP_CHECK(hipEventSynchronize(snap_ev_[l & 1]));  // this pinned buffer's last upload is done
+    std::memcpy(snap_host_[l & 1], (const char*)data + (size_t)l * lb, lb);
+    HIP_CHECK(hipMemcpyAsync(snap_dev_, snap_host_[l & 1], lb, hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipEventRecord(snap_ev_[l & 1], stream_));
+    snap_launch(slot, l, n_tokens, true);
+  }
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  // decode rows of the slot: their host positions are not beyond the restored length (advance_rows maps from there)
+  for (size_t b = 0; b < row_slots_.size(); ++b)
+    if (row_slots_[b] == slot) row_pos_[b] = std::min(row_pos_[b], n_tokens);
+  bt_dirty_ = true;
+  kv_sync((int)std::min(row_slots_.size(), (size_t)cfg_.max_batch));
 }
 
 std::vector<int> Engine::block_table(int slot) const {

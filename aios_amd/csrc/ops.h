@@ -361,6 +361,33 @@ struct KvShiftArgs {
 };
 void launch_kv_shift(const KvShiftArgs& a, hipStream_t st);
 
+// ---- KV snapshot -------------------------------------------------------------------------------
+// pack: positions [0, n_tokens) of a slot, read through row `slot` of the block table, written to one contiguous
+// buffer [layer][K, V][kv_head][token][head_dim] in the cache's own element type -- the layout Engine::kv_read
+// returns, which is the definition of the payload (tests/kv_snapshot_oracle.py is this rule in numpy).  unpack:
+// the reverse, into the slot's mapped blocks (Engine::kv_restore maps and un-shares them first).  Bytes move
+// verbatim, 16 at a time.  A (block, kv head) tile of a pool is contiguous and so is its place in the buffer, so
+// workgroup (block j, kv head, K or V, layer) copies min(KV_BLOCK, n_tokens - j * KV_BLOCK) rows from one to the
+// other: rows at or above n_tokens and blocks outside the row's [0, ceil(n_tokens / KV_BLOCK)) are neither read
+// nor written.  A table entry outside the pool is skipped: pack reads blocks [0, n_blocks] (n_blocks: the null
+// block an unmapped entry names), unpack writes blocks [0, n_blocks) only.  One launch covers layers
+// [layer0, layer0 + n_layers); the buffer starts at layer0.  kernels/kv_snapshot.hip.
+struct KvSnapArgs {
+  void* k_cache;           // layer 0's pools
+  void* v_cache;
+  size_t layer_bytes;      // bytes from one layer's pool to the next
+  void* buf;               // [n_layers][2][n_kv_heads][n_tokens][head_dim], 16-byte aligned
+  const int* block_table;  // [slots][max_blocks]
+  int max_blocks;
+  int n_blocks;            // allocatable blocks of a layer pool (block n_blocks: the null block)
+  int slot;
+  int layer0, n_layers, n_kv_heads, head_dim;
+  int n_tokens;
+  int elem_bytes;          // 2 (bf16) or 1 (fp8)
+  int unpack;              // 0: pool -> buf, 1: buf -> pool
+};
+void launch_kv_snapshot(const KvSnapArgs& a, hipStream_t st);
+
 // ---- MFMA GEMM (prefill) ----------------------------------------------------------------------
 // C[M][N] (fp32, epilogue) = A[M][K] (bf16) x W[N][K]^T (quantized, dequantized tile-wise in LDS)
 struct GemmArgs {

@@ -355,6 +355,10 @@ class TPEngine:
             # accept step is not broadcast to the workers): hidden, so the scheduler sees a tier that cannot
             # speculate, decodes plainly, logs that once and reports 0 / 0 drafted
             raise AttributeError(name)
+        if name in ("kv_save", "kv_restore"):
+            # no KV snapshots of a tensor-parallel tier (the shard's Engine.kv_save throws; each rank holds its
+            # own heads): hidden, so the scheduler refuses the slot actions and /slots answers 400
+            raise AttributeError(name)
         attr = getattr(self._eng, name)
         if name not in self._FORWARD or not callable(attr):
             return attr
@@ -527,6 +531,22 @@ def spec_context_shift(path: str) -> bool:
         if k == "ctxshift":
             return v not in ("0", "false", "no", "off")
     return False
+
+
+def spec_slot_snapshots(path: str):
+    """the '#...&slotsave=<dir>&kvrestore=<file>,<file>' fragments of a model spec (both percent-quoted): the
+    tier's KV snapshot directory ("" = the /slots actions are off) and the files restored into free slots after
+    the load (utils.config: slot_save_path, kv_restore)"""
+    from urllib.parse import unquote
+
+    save, files = "", []
+    for kv in filter(None, path.partition("#")[2].split("&")):
+        k, _, v = kv.partition("=")
+        if k == "slotsave":
+            save = unquote(v)
+        elif k == "kvrestore":
+            files = [unquote(f) for f in v.split(",") if f]
+    return save, files
 
 
 def parse_spec(path: str):

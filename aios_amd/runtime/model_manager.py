@@ -82,6 +82,7 @@ class ManagedModel:
     device: int = -1                  # GPU of this engine (-1: the manager's default device)
     group: str = ""                   # replica group (tier name); "" = the model's own name
     idle_unload_s: float = 0.0        # unload after this long without a request (0 = never)
+    slot_save_path: str = ""          # KV snapshot directory of the /slots actions ("" = off: they answer 501)
 
     def status_string(self) -> str:
         return f"error: {self.error}" if self.status == "error" else self.status
@@ -188,7 +189,7 @@ class ModelManager:
 
         E = native.require()
         from ..parallel.tp import (launch_tp, parse_spec, spec_kv_calibrate, spec_kv_dtype, spec_sampling,
-                                   spec_context_shift, spec_speculative)
+                                   spec_context_shift, spec_slot_snapshots, spec_speculative)
 
         device = self.device if m.device < 0 else m.device
 
@@ -264,6 +265,29 @@ class ModelManager:
         if capture is not None and os.environ.get("AIOS_GRAPH_WARMUP", "1") != "0":
             capture(m.scheduler.max_batch)
         m.weight_bytes, m.kv_bytes = eng.weight_bytes, eng.kv_bytes
+        m.slot_save_path, warm = spec_slot_snapshots(m.path)
+        if warm:
+            self._warm_start(m, warm)
+
+    @staticmethod
+    def _warm_start(m: ManagedModel, files: List[str]):
+        """Restore the tier's kv_restore files from its slot_save_path into free, empty slots (every load, the
+        auto-reload after a fault included).  A file that is missing or does not match is logged and skipped: a
+        warm start never fails the load."""
+        from . import kv_snapshot
+
+        sch = m.scheduler
+        for name in files:
+            try:
+                path = kv_snapshot.snapshot_path(m.slot_save_path, name)
+                slot = next((s["id"] for s in sch.slots() if not s["is_processing"] and not s["n_cached"]), None)
+                if slot is None:
+                    log.warning("%s: kv_restore: no empty slot left for %s; skipped", m.name, name)
+                    continue
+                got = sch.restore_slot(slot, path)
+                log.info("%s: kv_restore: %s -> slot %d (%d tokens)", m.name, name, slot, got["n_restored"])
+            except Exception as e:  # noqa: BLE001 - logged and skipped
+                log.warning("%s: kv_restore: %s skipped (%s: %s)", m.name, name, type(e).__name__, e)
 
     # ------------------------------------------------------------------ tier lifecycle
     def register_on_demand(self, name: str, path: str, context_length: int = 0, devices: Optional[List[int]] = None,

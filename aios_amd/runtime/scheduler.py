@@ -26,6 +26,7 @@ thread-safe callbacks.
 from __future__ import annotations
 
 import collections
+import concurrent.futures
 import dataclasses
 import logging
 import os
@@ -36,6 +37,7 @@ from typing import Callable, Deque, Dict, List, Optional
 import numpy as np
 
 from . import embedding as host_embedding
+from . import kv_snapshot
 from . import sampler as host_sampler
 from . import speculative as speculative_mod
 
@@ -145,6 +147,14 @@ class GenResult:
 SPEC_DEFAULTS = dict(mode="off", draft_max=7, ngram_min=2, ngram_max=3, max_context=4096)
 
 
+class SlotBusy(RuntimeError):
+    """a slot action (save / restore / erase) on a slot that is decoding or prefilling"""
+
+
+class SlotsUnsupported(RuntimeError):
+    """slot actions on a tier whose engine has no kv_save / kv_restore (a tensor-parallel or CPU tier)"""
+
+
 class _Seq:
     __slots__ = ("req", "slot", "pos", "last", "out", "grammar_state", "emitted", "t_first", "cached", "todo",
                  "p_off", "r_off", "seed", "proc", "pen_n", "bias", "bias_soft", "lp_n", "lps", "embedding", "plp_n", "plps",
@@ -193,6 +203,11 @@ class Scheduler:
         self.context_shift = bool(context_shift)
         self.can_shift = hasattr(engine, "shift_context")
         self._warned_no_shift = False
+        # KV snapshots (save_slot / restore_slot / erase_slot / slots): they need the engine's kv_save and
+        # kv_restore, which the CPU and tensor-parallel tiers lack.  Actions wait here for the worker, which owns
+        # the engine and runs them between two iterations
+        self.can_snapshot = hasattr(engine, "kv_save") and hasattr(engine, "kv_restore")
+        self._ops: Deque = collections.deque()
         # speculative decoding (SPEC_DEFAULTS; off unless the tier or a request turns it on); it needs the
         # engine's spec_decode, which the CPU and tensor-parallel tiers lack: they decode plainly and say so once
         self.spec = dict(SPEC_DEFAULTS)
@@ -250,7 +265,8 @@ class Scheduler:
         self.stop_flag = False
         self.stats = dict(requests=0, tokens=0, prefill_tokens=0, cached_tokens=0, steps=0, batch_sum=0, errors=0,
                           embeddings=0, prompt_scores=0, spec_steps=0, spec_drafted=0, spec_accepted=0,
-                          bias_overridden=0, context_shifts=0, shifted_tokens=0)
+                          bias_overridden=0, context_shifts=0, shifted_tokens=0, slot_saves=0, slot_restores=0,
+                          slot_erases=0)
         # health / metrics (ModelManager.supervise and HealthCheck details)
         self.max_slots = max_slots
         self.last_progress = time.time()   # last completed admission or decode step
@@ -283,13 +299,94 @@ class Scheduler:
     def load(self) -> int:
         return len(self.queue) + len(self.active) + len(self.prefilling)
 
+    # ------------------------------------------------------------------ slot actions (KV snapshots)
+    def _slot_op(self, fn, timeout: float):
+        """Run fn() on the worker thread between two iterations and return its result (or raise its error)."""
+        fut: concurrent.futures.Future = concurrent.futures.Future()
+        with self.cv:
+            if self.stop_flag:
+                raise RuntimeError(f"{self.name}: the scheduler is closed")
+            self._ops.append((fn, fut))
+            self.cv.notify()
+        return fut.result(timeout)
+
+    def _free_slot(self, slot) -> int:
+        if isinstance(slot, bool) or not isinstance(slot, int) or slot not in self.slot_cache:
+            raise ValueError(f"unknown slot {slot!r}")
+        if slot not in self.free_slots:
+            raise SlotBusy("slot busy")
+        return slot
+
+    def _need_snapshots(self):
+        if not self.can_snapshot:
+            raise SlotsUnsupported("slots: single-GPU engines only")
+
+    def save_slot(self, slot: int, path: str, timeout: float = 120.0) -> dict:
+        """Save a free slot's cache to `path` (runtime/kv_snapshot.py): exactly the tokens its cache record holds
+        -- the positions _pick_slot would trust, so nothing behind a context shift's n_keep and nothing a dropped
+        pipelined step wrote.  {"n_saved": tokens, "n_written": bytes}.  SlotBusy for a slot that is decoding or
+        prefilling, ValueError for an unknown slot or an empty record."""
+        def op():
+            self._need_snapshots()
+            s = self._free_slot(slot)
+            n, written = kv_snapshot.save_slot(self.engine, s, list(self.slot_cache[s]), path, self.name)
+            self.stats["slot_saves"] += 1
+            return {"n_saved": n, "n_written": written}
+        return self._slot_op(op, timeout)
+
+    def restore_slot(self, slot: int, path: str, timeout: float = 120.0) -> dict:
+        """Restore `path` into a free slot and set its cache record to the file's tokens: the next request with that
+        prefix reuses it through the ordinary admission path.  {"n_restored": tokens, "n_read": bytes}.
+        FileNotFoundError, kv_snapshot.SnapshotError (naming the field) and SlotBusy change nothing."""
+        def op():
+            self._need_snapshots()
+            s = self._free_slot(slot)
+            tokens, size = kv_snapshot.restore_slot(self.engine, s, path, self.name, self.max_ctx)
+            self.slot_cache[s] = list(tokens)
+            self.stats["slot_restores"] += 1
+            return {"n_restored": len(tokens), "n_read": size}
+        return self._slot_op(op, timeout)
+
+    def erase_slot(self, slot: int, timeout: float = 120.0) -> dict:
+        """Release a free slot's blocks and clear its cache record.  {"n_erased": tokens the record held}."""
+        def op():
+            self._need_snapshots()
+            s = self._free_slot(slot)
+            n = len(self.slot_cache[s])
+            self.engine.release_slot(s)
+            self.slot_cache[s] = []
+            self.stats["slot_erases"] += 1
+            return {"n_erased": n}
+        return self._slot_op(op, timeout)
+
+    def slots(self, timeout: float = 120.0) -> List[dict]:
+        """One entry per slot: id, is_processing (decoding or prefilling) and n_cached (its cache record's length)."""
+        def op():
+            return [{"id": s, "is_processing": s not in self.free_slots, "n_cached": len(self.slot_cache[s])}
+                    for s in sorted(self.slot_cache)]
+        return self._slot_op(op, timeout)
+
+    def _run_ops(self, ops):
+        for fn, fut in ops:
+            if not fut.set_running_or_notify_cancel():
+                continue
+            try:
+                fut.set_result(fn())
+            except BaseException as e:  # noqa: BLE001 - the caller's to handle
+                fut.set_exception(e)
+
     # ------------------------------------------------------------------ worker
     def _run(self):
         while True:
             with self.cv:
-                while not self.stop_flag and not self.queue and not self.active and not self.prefilling:
+                while (not self.stop_flag and not self.queue and not self.active and not self.prefilling and
+                       not self._ops):
                     self.cv.wait(timeout=1.0)
+                ops = list(self._ops)
+                self._ops.clear()
                 if self.stop_flag:
+                    for _fn, fut in ops:
+                        fut.set_exception(RuntimeError(f"{self.name}: the scheduler is closed"))
                     self._discard_pending()
                     for s in list(self.active) + list(self.prefilling):
                         self._finish(s, "cancelled")
@@ -301,8 +398,10 @@ class Scheduler:
                 while (self.queue and self.free_slots and
                        len(self.active) + len(self.prefilling) + len(admit) < self.max_batch):
                     admit.append(self.queue.popleft())
-            if admit or self.prefilling:
+            if admit or self.prefilling or ops:
                 self._drain()  # (no other engine call while a pipelined step is in flight)
+            if ops:
+                self._run_ops(ops)
             for r in admit:
                 try:
                     self._admit(r)

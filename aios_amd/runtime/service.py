@@ -558,6 +558,8 @@ class AIRuntimeService:
         app.router.add_get("/v1/models", self._http_models)
         app.router.add_post("/v1/embeddings", self._http_embeddings)
         app.router.add_post("/v1/completions", self._http_completions)
+        app.router.add_get("/slots", self._http_slots)
+        app.router.add_post("/slots/{id}", self._http_slot_action)
         runner = web.AppRunner(app, access_log=None)
         await runner.setup()
         try:
@@ -756,6 +758,81 @@ class AIRuntimeService:
         n = sum(len(ids) for ids in inputs)
         return web.json_response({"object": "list", "data": data, "model": m.name,
                                   "usage": {"prompt_tokens": n, "total_tokens": n}})
+
+    async def _http_slots(self, request):
+        """llama-server's GET /slots: one entry per slot -- id, is_processing, n_cached (the tokens of its cache
+        record, what a save would write)."""
+        from aiohttp import web
+
+        m = request.app["model"]
+        return web.json_response(await asyncio.to_thread(m.scheduler.slots))
+
+    async def _http_slot_action(self, request):
+        """llama-server's POST /slots/{id}?action=save|restore|erase with body {"filename": "..."} (runtime/
+        kv_snapshot.py: the file; Scheduler.save_slot / restore_slot / erase_slot).  Files live in the tier's
+        slot_save_path and nowhere else; without one the actions answer 501, as llama-server does without
+        --slot-save-path."""
+        from aiohttp import web
+
+        from . import kv_snapshot
+        from .scheduler import SlotBusy, SlotsUnsupported
+
+        m = request.app["model"]
+
+        def err(status, msg, kind="invalid_request_error"):
+            return web.json_response({"error": {"message": msg, "type": kind, "code": status}}, status=status)
+
+        action = request.query.get("action", "")
+        if action not in ("save", "restore", "erase"):
+            return err(400, f"action: must be save, restore or erase, not {action!r}")
+        directory = getattr(m, "slot_save_path", "")
+        if not directory:
+            return err(501, "this server does not support slot actions: no slot_save_path is configured",
+                       "not_supported_error")
+        if not getattr(m.scheduler, "can_snapshot", False):
+            return err(400, "slots: single-GPU engines only")
+        try:
+            slot = int(request.match_info["id"])
+        except ValueError:
+            return err(400, f"unknown slot {request.match_info['id']!r}")
+        sch = m.scheduler
+        t0 = time.perf_counter()
+        try:
+            if action == "erase":
+                got = await asyncio.to_thread(sch.erase_slot, slot)
+                return web.json_response({"id_slot": slot, "n_erased": got["n_erased"]})
+            try:
+                body = await request.json()
+            except ValueError:
+                return err(400, "the body is not JSON")
+            if not isinstance(body, dict):
+                return err(400, "the body must be a JSON object")
+            filename = body.get("filename")
+            path = kv_snapshot.snapshot_path(directory, filename)
+            if action == "save":
+                try:
+                    got = await asyncio.to_thread(sch.save_slot, slot, path)
+                except kv_snapshot.SnapshotError as e:  # (a slot with nothing cached)
+                    return err(400, str(e))
+                return web.json_response({"id_slot": slot, "filename": filename, "n_saved": got["n_saved"],
+                                          "n_written": got["n_written"],
+                                          "timings": {"save_ms": (time.perf_counter() - t0) * 1e3}})
+            got = await asyncio.to_thread(sch.restore_slot, slot, path)
+            return web.json_response({"id_slot": slot, "filename": filename, "n_restored": got["n_restored"],
+                                      "n_read": got["n_read"],
+                                      "timings": {"restore_ms": (time.perf_counter() - t0) * 1e3}})
+        except SlotBusy as e:
+            return err(409, str(e))
+        except SlotsUnsupported as e:
+            return err(400, str(e))
+        except FileNotFoundError:
+            return err(404, f"filename: no snapshot {body.get('filename')!r}", "not_found_error")
+        except kv_snapshot.SnapshotError as e:  # the file does not fit this engine, or is damaged: the field is named
+            return err(409, f"snapshot mismatch: {e}")
+        except ValueError as e:  # an unknown slot, a malformed filename
+            return err(400, str(e))
+        except Exception as e:  # noqa: BLE001 - e.g. a pool without the blocks the restore needs
+            return err(500, f"{type(e).__name__}: {e}", "server_error")
 
     async def close(self):
         for r in self._http_runners.values():

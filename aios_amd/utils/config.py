@@ -64,6 +64,24 @@ class ModelTier:
     # context shift by default for the tier's requests (runtime/scheduler.py: GenRequest.context_shift): at the
     # context window the oldest tokens behind the prompt are dropped and generation goes on; single-GPU tiers
     context_shift: bool = False
+    # KV snapshots (runtime/kv_snapshot.py; llama-server's --slot-save-path): the directory the tier's
+    # POST /slots/{id}?action=save|restore reads and writes ("" = models.slot_save_path; both unset: the actions
+    # answer 501), and snapshot files in it restored into free slots after every load of the tier, the
+    # auto-reload after a fault included (a missing or mismatching file is logged and skipped); single-GPU tiers
+    slot_save_path: str = ""
+    kv_restore: List[str] = dataclasses.field(default_factory=list)
+
+    def snapshot_frag(self, node_path: str = "") -> List[str]:
+        """the KV snapshot settings as model-spec fragments (parallel.tp.spec_slot_snapshots)"""
+        from urllib.parse import quote
+
+        path = self.slot_save_path or node_path
+        if not path:
+            return []
+        out = ["slotsave=" + quote(path, safe="/")]
+        if self.kv_restore:
+            out.append("kvrestore=" + ",".join(quote(f, safe="") for f in self.kv_restore))
+        return out
 
     def speculative_frag(self) -> List[str]:
         """the non-default speculative settings as model-spec fragments (parallel.tp.spec_speculative)"""
@@ -95,6 +113,7 @@ class ModelsConfig:
     devices: List[int] = dataclasses.field(default_factory=list)
     max_batch: int = 16
     max_slots: int = 16
+    slot_save_path: str = ""    # KV snapshot directory of every tier without its own (ModelTier.slot_save_path); "" = off
     tiers: Dict[str, ModelTier] = dataclasses.field(default_factory=dict)
 
 
@@ -177,6 +196,7 @@ class NodeConfig:
             frag += t.speculative_frag()
             if t.context_shift:
                 frag.append("ctxshift=1")
+            frag += t.snapshot_frag(self.models.slot_save_path)
             devs = list(t.devices)
             if not devs and t.replicas > 1:
                 devs = list(self.models.devices[:t.replicas]) or list(range(t.replicas))
@@ -219,6 +239,7 @@ class NodeConfig:
             frag += t.speculative_frag()
             if t.context_shift:
                 frag.append("ctxshift=1")
+            frag += t.snapshot_frag(self.models.slot_save_path)
             out.append((name, path + ("#" + "&".join(frag) if frag else ""), t.context_length))
         return out
 
@@ -229,6 +250,12 @@ def _coerce(cls, raw: Dict[str, Any], warnings: List[str], where: str):
     for k, v in raw.items():
         f = fields.get(k)
         if f is None or k == "tiers":
+            continue
+        if k == "kv_restore":
+            if isinstance(v, list) and all(isinstance(x, str) for x in v):
+                kw[k] = list(v)
+            else:
+                warnings.append(f"{where}.{k}: cannot use {v!r} (a list of file names); default kept")
             continue
         if k == "devices":
             if isinstance(v, list):

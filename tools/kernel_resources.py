@@ -38,6 +38,7 @@ HOT = [
     "aios::get_rows_step_kernel*",
     "aios::spec_accept_kernel*",
     "aios::kv_shift_kernel<*",
+    "aios::kv_snapshot_kernel<*",
 ]
 
 
