@@ -324,6 +324,43 @@ PYBIND11_MODULE(_engine, m) {
            py::arg("bias_ids") = std::vector<std::vector<int>>{},
            py::arg("bias_vals") = std::vector<std::vector<float>>{}, py::call_guard<py::gil_scoped_release>())
       .def("set_logprobs", &Engine::set_logprobs, py::arg("top_n"))
+      .def("grammar_vocab",
+           [](Engine& e, const std::vector<py::bytes>& toks, const std::vector<int>& eos_ids) {
+             std::vector<std::string> t;
+             t.reserve(toks.size());
+             for (auto& b : toks) t.push_back(std::string(b));
+             py::gil_scoped_release nogil;
+             e.grammar_vocab(t, eos_ids);
+           },
+           py::arg("tokens"), py::arg("eos_ids"))
+      .def("grammar_load",
+           [](Engine& e, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> byte_class,
+              py::array_t<uint16_t, py::array::c_style | py::array::forcecast> trans,
+              py::array_t<uint8_t, py::array::c_style | py::array::forcecast> accept) {
+             if (byte_class.ndim() != 1 || byte_class.shape(0) != 256 || trans.ndim() != 2 || accept.ndim() != 1 ||
+                 accept.shape(0) != trans.shape(0))
+               throw std::runtime_error("grammar_load: byte_class[256], trans[S][C], accept[S] expected");
+             const uint8_t* bc = byte_class.data();
+             const uint16_t* tr = trans.data();
+             const uint8_t* ac = accept.data();
+             const int S = (int)trans.shape(0), C = (int)trans.shape(1);
+             py::gil_scoped_release nogil;
+             return e.grammar_load(bc, tr, ac, S, C);
+           },
+           py::arg("byte_class"), py::arg("trans"), py::arg("accept"))
+      .def("grammar_free", &Engine::grammar_free, py::arg("gid"), py::call_guard<py::gil_scoped_release>())
+      .def("grammar_masks",
+           [](Engine& e, int gid, const std::vector<int>& states) {
+             std::vector<uint8_t> m;
+             {
+               py::gil_scoped_release nogil;
+               m = e.grammar_masks(gid, states);
+             }
+             return py::bytes((const char*)m.data(), m.size());
+           },
+           py::arg("gid"), py::arg("states"))
+      .def("set_grammar_rows", &Engine::set_grammar_rows, py::arg("gids"), py::arg("states"))
+      .def_property_readonly("grammars_loaded", &Engine::grammars_loaded)
       .def("last_logprobs",
            [](const Engine& e) -> py::object {
              // () when the last sampler launch had none staged, else (token_lp [B], ids [B][LOGPROB_MAX_TOP],
@@ -927,6 +964,38 @@ PYBIND11_MODULE(_engine, m) {
         },
         py::arg("in_tokens"), py::arg("out_tokens"), py::arg("pos0"), py::arg("R"), py::arg("record"), py::arg("tokens"),
         py::arg("pos"), py::arg("seq_len"), py::arg("history"), py::arg("hist_stride"), py::arg("st"));
+  m.attr("GRAMMAR_MAX") = GRAMMAR_MAX;
+  m.attr("GRAMMAR_MAX_EOS") = GRAMMAR_MAX_EOS;
+  m.def("grammar_tables",
+        [](const std::vector<std::tuple<uintptr_t, uintptr_t, uintptr_t, int, int>>& grammars) {
+          // the bytes of a GrammarTable array for grammar_mask's `grammars` (the caller copies them to the device):
+          // one (byte_class[256] u8, trans[S][C] u16, accept[S] u8, S, C) of device pointers per grammar
+          std::vector<GrammarTable> host;
+          for (const auto& g : grammars)
+            host.push_back(GrammarTable{(const uint8_t*)std::get<0>(g), (const uint16_t*)std::get<1>(g),
+                                        (const uint8_t*)std::get<2>(g), std::get<3>(g), std::get<4>(g)});
+          return py::bytes((const char*)host.data(), host.size() * sizeof(GrammarTable));
+        },
+        py::arg("grammars"));
+  m.def("grammar_mask",
+        [](uintptr_t tok_off, uintptr_t tok_bytes, int V, uintptr_t grammars, int n_grammars, uintptr_t gid,
+           uintptr_t state, uintptr_t mask, int B, bool fill_free, const std::vector<int>& eos, uintptr_t st) {
+          // tok_off: [V + 1] ints, tok_bytes: u8; grammars: the caller's device copy of grammar_tables(...), whose
+          // tables' entries the caller has checked (ops.h); gid / state: [B] ints; mask: [B][ceil(V / 8)]
+          if (n_grammars > GRAMMAR_MAX || eos.size() > (size_t)GRAMMAR_MAX_EOS)
+            throw std::runtime_error("grammar_mask: too many grammars or end-of-sequence ids");
+          GrammarMaskArgs a;
+          std::memset(&a, 0, sizeof(a));
+          a.tok_off = (const int*)tok_off; a.tok_bytes = (const uint8_t*)tok_bytes; a.V = V;
+          a.grammars = (const GrammarTable*)grammars; a.n_grammars = n_grammars;
+          a.gid = (const int*)gid; a.state = (const int*)state; a.mask = (uint8_t*)mask; a.B = B;
+          a.fill_free = fill_free ? 1 : 0;
+          a.n_eos = (int)eos.size();
+          for (int j = 0; j < GRAMMAR_MAX_EOS; ++j) a.eos[j] = j < a.n_eos ? eos[j] : -1;
+          launch_grammar_mask(a, S(st));
+        },
+        py::arg("tok_off"), py::arg("tok_bytes"), py::arg("V"), py::arg("grammars"), py::arg("n_grammars"), py::arg("gid"),
+        py::arg("state"), py::arg("mask"), py::arg("B"), py::arg("fill_free"), py::arg("eos"), py::arg("st"));
   m.def("kv_snapshot",
         [](uintptr_t k_cache, uintptr_t v_cache, size_t layer_bytes, uintptr_t buf, uintptr_t block_table, int max_blocks,
            int n_blocks, int slot, int n_tokens, int n_layers, int n_kv_heads, int head_dim, int elem_bytes, bool unpack,

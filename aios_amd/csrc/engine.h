@@ -241,6 +241,32 @@ class Engine {
   };
   Logprobs last_logprobs() const;
 
+  // DFA grammars (ops.h GrammarMaskArgs: the rule): a row's allowed-token mask computed on the device from
+  // (grammar id, state) -- no host walk, no memo, no per-step mask upload.
+  // grammar_vocab: the vocabulary's byte strings (vocab_size of them, empty for a control token: what JsonGrammar
+  // receives) and its end-of-sequence ids, uploaded once; calling it again drops nothing but replaces the table.
+  // grammar_load: uploads one grammar's tables and returns its id (ids of freed grammars are reused).  Refuses,
+  // before anything is kept: a table that is not [n_states][n_classes] with 2 <= n_states <= 65535 and 1 <=
+  // n_classes <= 256, a class or transition out of range, a dead state 0 with a way out, GRAMMAR_MAX grammars
+  // already loaded, no vocabulary, and -- after one grammar_masks pass over every state -- a live state that is
+  // not terminal (accepting with no way on) and allows no token: no tokenizer path leads on from there.
+  // grammar_free: waits for the stream, then frees the tables.  grammar_masks: the masks of `states`, one row
+  // each, ceil(V / 8) bytes per row (one launch per GRAMMAR_MASK_ROWS rows, into a buffer of its own).
+  // set_grammar_rows: the rows' (grammar id or -1, state) for the NEXT sampler launch only -- decode,
+  // decode_sample, sample_first or resample -- with set_sample_processors' lifetime: one shot, refused and dropped
+  // when staged for another row count, dropped by a call that throws before its launch, by decode_loop_run and
+  // by spec_decode (grammar rows take no speculative steps).  At that launch the mask kernel goes on the
+  // stream behind the host mask's copy, if the call has one, and in front of the sampler (or of the step graph
+  // that holds it), and the sampler runs masked: rows with id -1 keep the host's mask bytes, or are set to all
+  // ones when the call passed no mask.  A state must be a live state of its grammar.  Single-GPU engines only.
+  static constexpr int GRAMMAR_MASK_ROWS = 1024;
+  void grammar_vocab(const std::vector<std::string>& tokens, const std::vector<int>& eos_ids);
+  int grammar_load(const uint8_t* byte_class, const uint16_t* trans, const uint8_t* accept, int n_states, int n_classes);
+  void grammar_free(int gid);
+  std::vector<uint8_t> grammar_masks(int gid, const std::vector<int>& states);
+  void set_grammar_rows(const std::vector<int>& gids, const std::vector<int>& states);
+  int grammars_loaded() const;
+
   // Device-resident greedy generation for benchmarking: runs n_steps decode steps for B
   // sequences without host synchronisation (tokens fed back on device, graph replay when
   // use_graph).  Sequences must already be prefilled to positions pos[b].
@@ -364,13 +390,33 @@ class Engine {
     Engine& e;
     SampleStage(Engine& eng, int B, const char* who) : e(eng) {
       const char* bad = e.proc_rows_ && e.proc_rows_ != B ? "sample processors"
-                        : e.lp_rows_ && e.lp_rows_ != B   ? "logprobs" : nullptr;
+                        : e.lp_rows_ && e.lp_rows_ != B   ? "logprobs"
+                        : e.gr_rows_ && e.gr_rows_ != B   ? "grammar rows" : nullptr;
       if (!bad) return;
-      e.proc_rows_ = e.lp_rows_ = 0;
+      e.proc_rows_ = e.lp_rows_ = e.gr_rows_ = 0;
       throw std::runtime_error(std::string(who) + ": " + bad + " staged for another batch size");
     }
-    ~SampleStage() { e.proc_rows_ = e.lp_rows_ = 0; }
+    ~SampleStage() { e.proc_rows_ = e.lp_rows_ = e.gr_rows_ = 0; }
   };
+  // DFA grammars: the vocabulary table, the loaded grammars (one device buffer each) and their device descriptors,
+  // the staged rows (pinned, two halves: a staging may follow one whose copy is still queued)
+  struct GrammarSlot {
+    void* buf = nullptr;  // byte_class[256] | trans | accept
+    int n_states = 0, n_classes = 0;
+  };
+  std::vector<GrammarSlot> grammars_;
+  GrammarTable* d_grammars_ = nullptr;   // [GRAMMAR_MAX]
+  int* d_tok_off_ = nullptr;             // [V + 1]
+  uint8_t* d_tok_bytes_ = nullptr;
+  int gr_eos_[GRAMMAR_MAX_EOS] = {0};
+  int gr_n_eos_ = 0;
+  int* h_gr_ = nullptr;                  // pinned [2][2][max_batch]: gid | state
+  int* d_gr_ = nullptr;                  // [2][max_batch]
+  int gr_rows_ = 0, gr_buf_ = 0;         // rows staged by set_grammar_rows (0: none) and the half they are in
+  GrammarMaskArgs grammar_args(int B, const int* gid, const int* state, uint8_t* mask, bool fill_free) const;
+  // the staged grammar rows of a B-row sampler launch: their upload and the mask kernel, un-staged; false when
+  // nothing is staged (host_mask: the call copied mask bytes of its own into d_mask_)
+  bool take_grammar(int B, bool host_mask);
   std::vector<int> lp_last_;             // top_n of the rows the last sampler launch reported (empty: none)
   char* h_lp_ = nullptr;                 // pinned: [max_batch] top_n | the device output block's mirror
   char* d_lp_out_ = nullptr;             // [max_batch][LOGPROB_ROW] floats | [max_batch][LOGPROB_ROW] ids

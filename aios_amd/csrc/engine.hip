@@ -106,6 +106,10 @@ Engine::~Engine() {
   if (h_mask_) hipHostFree(h_mask_);
   if (h_proc_) hipHostFree(h_proc_);
   if (h_lp_) hipHostFree(h_lp_);
+  if (h_gr_) hipHostFree(h_gr_);
+  if (d_tok_bytes_) hipFree(d_tok_bytes_);
+  for (auto& g : grammars_)
+    if (g.buf) hipFree(g.buf);
   if (h_spec_) hipHostFree(h_spec_);
   if (snap_dev_) hipFree(snap_dev_);
   for (void* h : snap_host_)
@@ -1313,6 +1317,199 @@ Engine::Logprobs Engine::last_logprobs() const {
   return r;
 }
 
+// ---- DFA grammars ------------------------------------------------------------------------------
+void Engine::grammar_vocab(const std::vector<std::string>& tokens, const std::vector<int>& eos_ids) {
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  if (cfg_.tp_size > 1) throw std::runtime_error("grammar_vocab: not available on a tensor-parallel engine");
+  const int V = cfg_.vocab_size;
+  if ((int)tokens.size() != V) throw std::runtime_error("grammar_vocab: " + std::to_string(V) + " tokens expected");
+  if ((int)eos_ids.size() > GRAMMAR_MAX_EOS)
+    throw std::runtime_error("grammar_vocab: more than " + std::to_string(GRAMMAR_MAX_EOS) + " end-of-sequence ids");
+  for (int e : eos_ids)
+    if (e < 0 || e >= V) throw std::runtime_error("grammar_vocab: end-of-sequence id out of range");
+  std::vector<int> off(V + 1, 0);
+  size_t total = 0;
+  for (int t = 0; t < V; ++t) {
+    total += tokens[t].size();
+    if (total > (size_t)INT32_MAX) throw std::runtime_error("grammar_vocab: vocabulary bytes overflow");
+    off[t + 1] = (int)total;
+  }
+  std::vector<uint8_t> bytes(std::max<size_t>(total, 1), 0);
+  for (int t = 0; t < V; ++t) std::memcpy(bytes.data() + off[t], tokens[t].data(), tokens[t].size());
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  HIP_CHECK(hipStreamSynchronize(stream_));  // (a launch reading the old table may be queued)
+  if (!d_grammars_) {
+    const int Bm = cfg_.max_batch;
+    grammars_.assign(GRAMMAR_MAX, GrammarSlot{});
+    d_grammars_ = (GrammarTable*)dmalloc(sizeof(GrammarTable) * GRAMMAR_MAX);
+    HIP_CHECK(hipMemset(d_grammars_, 0, sizeof(GrammarTable) * GRAMMAR_MAX));
+    d_gr_ = (int*)dmalloc((size_t)2 * Bm * 4);
+    d_tok_off_ = (int*)dmalloc((size_t)(V + 1) * 4);
+    HIP_CHECK(hipHostMalloc((void**)&h_gr_, (size_t)4 * Bm * 4, hipHostMallocDefault));
+  }
+  if (d_tok_bytes_) HIP_CHECK(hipFree(d_tok_bytes_));
+  d_tok_bytes_ = nullptr;
+  HIP_CHECK(hipMalloc((void**)&d_tok_bytes_, bytes.size()));
+  HIP_CHECK(hipMemcpy(d_tok_bytes_, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(d_tok_off_, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+  gr_n_eos_ = (int)eos_ids.size();
+  for (int j = 0; j < GRAMMAR_MAX_EOS; ++j) gr_eos_[j] = j < gr_n_eos_ ? eos_ids[j] : -1;
+}
+
+int Engine::grammars_loaded() const {
+  int n = 0;
+  for (const auto& g : grammars_) n += g.buf != nullptr;
+  return n;
+}
+
+GrammarMaskArgs Engine::grammar_args(int B, const int* gid, const int* state, uint8_t* mask, bool fill_free) const {
+  GrammarMaskArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.tok_off = d_tok_off_; a.tok_bytes = d_tok_bytes_; a.V = cfg_.vocab_size;
+  a.grammars = d_grammars_; a.n_grammars = GRAMMAR_MAX;
+  a.gid = gid; a.state = state; a.mask = mask; a.B = B;
+  a.fill_free = fill_free ? 1 : 0;
+  for (int j = 0; j < GRAMMAR_MAX_EOS; ++j) a.eos[j] = gr_eos_[j];
+  a.n_eos = gr_n_eos_;
+  return a;
+}
+
+int Engine::grammar_load(const uint8_t* byte_class, const uint16_t* trans, const uint8_t* accept, int n_states,
+                         int n_classes) {
+  if (!d_tok_bytes_) throw std::runtime_error("grammar_load: no vocabulary (grammar_vocab first)");
+  const int S = n_states, C = n_classes;
+  if (S < 2 || S > 65535 || C < 1 || C > 256) throw std::runtime_error("grammar_load: table shape out of range");
+  for (int c = 0; c < 256; ++c)
+    if (byte_class[c] >= C) throw std::runtime_error("grammar_load: byte class out of range");
+  for (size_t i = 0; i < (size_t)S * C; ++i) {
+    if (trans[i] >= S) throw std::runtime_error("grammar_load: transition out of range");
+    if (i < (size_t)C && trans[i] != 0) throw std::runtime_error("grammar_load: the dead state 0 has a way out");
+  }
+  int gid = -1;
+  for (int i = 0; i < GRAMMAR_MAX && gid < 0; ++i)
+    if (!grammars_[i].buf) gid = i;
+  if (gid < 0) throw std::runtime_error("grammar_load: " + std::to_string(GRAMMAR_MAX) + " grammars already loaded");
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  const size_t t_off = 256, a_off = t_off + (size_t)S * C * 2;
+  std::vector<uint8_t> host(a_off + S);
+  std::memcpy(host.data(), byte_class, 256);
+  std::memcpy(host.data() + t_off, trans, (size_t)S * C * 2);
+  std::memcpy(host.data() + a_off, accept, S);
+  GrammarSlot& g = grammars_[gid];
+  HIP_CHECK(hipMalloc(&g.buf, host.size()));
+  g.n_states = S;
+  g.n_classes = C;
+  const char* base = (const char*)g.buf;
+  const GrammarTable tab{(const uint8_t*)base, (const uint16_t*)(base + t_off), (const uint8_t*)(base + a_off), S, C};
+  try {
+    HIP_CHECK(hipMemcpy(g.buf, host.data(), host.size(), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_grammars_ + gid, &tab, sizeof(tab), hipMemcpyHostToDevice));
+    // every live state that is not terminal must allow a token
+    std::vector<int> states;
+    for (int s = 1; s < S; ++s) {
+      bool way_on = false;
+      for (int c = 0; c < C && !way_on; ++c) way_on = trans[(size_t)s * C + c] != 0;
+      if (way_on || !accept[s]) states.push_back(s);
+    }
+    const size_t nb = (size_t)((cfg_.vocab_size + 7) / 8);
+    for (size_t i0 = 0; i0 < states.size(); i0 += GRAMMAR_MASK_ROWS) {
+      const size_t n = std::min(states.size() - i0, (size_t)GRAMMAR_MASK_ROWS);
+      const std::vector<uint8_t> m = grammar_masks(gid, std::vector<int>(states.begin() + i0, states.begin() + i0 + n));
+      for (size_t r = 0; r < n; ++r) {
+        bool any = false;
+        for (size_t j = 0; j < nb && !any; ++j) any = m[r * nb + j] != 0;
+        if (!any)
+          throw std::runtime_error("grammar_load: state " + std::to_string(states[i0 + r]) +
+                                   " allows no token of this vocabulary");
+      }
+    }
+  } catch (...) {
+    // (the descriptor first, as grammar_free does: nothing on the device names the freed buffer)
+    const GrammarTable none{nullptr, nullptr, nullptr, 0, 0};
+    hipStreamSynchronize(stream_);
+    hipMemcpy(d_grammars_ + gid, &none, sizeof(none), hipMemcpyHostToDevice);
+    hipFree(g.buf);
+    g = GrammarSlot{};
+    throw;
+  }
+  return gid;
+}
+
+void Engine::grammar_free(int gid) {
+  if (gid < 0 || gid >= (int)grammars_.size() || !grammars_[gid].buf) throw std::runtime_error("grammar_free: unknown grammar");
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  HIP_CHECK(hipStreamSynchronize(stream_));  // (a launch reading the tables may be queued)
+  const GrammarTable none{nullptr, nullptr, nullptr, 0, 0};
+  HIP_CHECK(hipMemcpy(d_grammars_ + gid, &none, sizeof(none), hipMemcpyHostToDevice));
+  HIP_CHECK(hipFree(grammars_[gid].buf));
+  grammars_[gid] = GrammarSlot{};
+}
+
+std::vector<uint8_t> Engine::grammar_masks(int gid, const std::vector<int>& states) {
+  const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
+  if (gid < 0 || gid >= (int)grammars_.size() || !grammars_[gid].buf) throw std::runtime_error("grammar_masks: unknown grammar");
+  for (int s : states)
+    if (s < 0 || s >= grammars_[gid].n_states) throw std::runtime_error("grammar_masks: state out of range");
+  const size_t n = states.size(), nb = (size_t)((cfg_.vocab_size + 7) / 8);
+  std::vector<uint8_t> out(n * nb);
+  if (!n) return out;
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  const size_t rows = std::min(n, (size_t)GRAMMAR_MASK_ROWS);
+  char* dev = nullptr;  // [rows] gid | [rows] state | [rows][nb] masks
+  HIP_CHECK(hipMalloc((void**)&dev, rows * 8 + rows * nb));
+  try {
+    std::vector<int> rs(2 * rows);
+    for (size_t i0 = 0; i0 < n; i0 += rows) {
+      const size_t k = std::min(rows, n - i0);
+      for (size_t r = 0; r < k; ++r) {
+        rs[r] = gid;
+        rs[rows + r] = states[i0 + r];
+      }
+      HIP_CHECK(hipMemcpyAsync(dev, rs.data(), rows * 8, hipMemcpyHostToDevice, stream_));
+      launch_grammar_mask(grammar_args((int)k, (const int*)dev, (const int*)dev + rows, (uint8_t*)dev + rows * 8, true),
+                          stream_);
+      HIP_CHECK(hipMemcpyAsync(out.data() + i0 * nb, dev + rows * 8, k * nb, hipMemcpyDeviceToHost, stream_));
+      HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+  } catch (...) {
+    hipFree(dev);
+    throw;
+  }
+  HIP_CHECK(hipFree(dev));
+  return out;
+}
+
+void Engine::set_grammar_rows(const std::vector<int>& gids, const std::vector<int>& states) {
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  if (!d_tok_bytes_) throw std::runtime_error("set_grammar_rows: no vocabulary (grammar_vocab first)");
+  const int B = (int)gids.size(), Bm = cfg_.max_batch;
+  if (B < 1 || B > Bm) throw std::runtime_error("set_grammar_rows: batch out of range");
+  if ((int)states.size() != B) throw std::runtime_error("set_grammar_rows: size mismatch");
+  for (int b = 0; b < B; ++b) {
+    if (gids[b] < 0) continue;
+    if (gids[b] >= (int)grammars_.size() || !grammars_[gids[b]].buf)
+      throw std::runtime_error("set_grammar_rows: unknown grammar");
+    if (states[b] < 1 || states[b] >= grammars_[gids[b]].n_states)
+      throw std::runtime_error("set_grammar_rows: state out of range");
+  }
+  gr_buf_ ^= 1;
+  int* h = h_gr_ + (size_t)gr_buf_ * 2 * Bm;
+  for (int b = 0; b < B; ++b) {
+    h[b] = gids[b] < 0 ? -1 : gids[b];
+    h[Bm + b] = gids[b] < 0 ? 0 : states[b];
+  }
+  gr_rows_ = B;
+}
+
+bool Engine::take_grammar(int B, bool host_mask) {
+  if (!gr_rows_) return false;
+  gr_rows_ = 0;  // one shot (the caller's SampleStage checked the rows)
+  const int Bm = cfg_.max_batch;
+  HIP_CHECK(hipMemcpyAsync(d_gr_, h_gr_ + (size_t)gr_buf_ * 2 * Bm, (size_t)2 * Bm * 4, hipMemcpyHostToDevice, stream_));
+  launch_grammar_mask(grammar_args(B, d_gr_, d_gr_ + Bm, d_mask_, !host_mask), stream_);
+  return true;
+}
+
 SampleArgs Engine::sample_args(int B, bool masked) const {
   SampleArgs s;
   std::memset(&s, 0, sizeof(s));
@@ -1751,7 +1948,7 @@ std::vector<int> Engine::decode(const std::vector<int>& slots, const std::vector
   const int B = (int)slots.size();
   const SampleStage stage(*this, B, "decode");  // (before the step changes any state)
   check_step("decode", slots, tokens, pos, seeds, true);
-  const bool masked = !mask.empty();
+  bool masked = !mask.empty();
   if (masked && mask.size() != (size_t)B * ((cfg_.vocab_size + 7) / 8))
     throw std::runtime_error("decode: mask size mismatch");
   row_slots_ = slots;
@@ -1759,6 +1956,7 @@ std::vector<int> Engine::decode(const std::vector<int>& slots, const std::vector
   // one pinned staging block -> one async copy; the device-resident seed lets one captured graph per
   // (B, masked) serve every request
   upload_step_params(slots, tokens, pos, temperature, top_k, top_p, seed, seeds, mask);
+  if (take_grammar(B, masked)) masked = true;  // (behind the mask's copy, in front of the graph that samples)
   if (proc_rows_ || lp_rows_) {
     // staged logit processors / logprobs: the forward graph and an eager sampler (and logprob launch), as
     // the pipelined path runs a step -- the captured (B, masked) step graphs never see them
@@ -1833,7 +2031,8 @@ std::vector<int> Engine::resample(int B, const std::vector<float>& temperature, 
   if (!mask.empty() && mask.size() != mbytes) throw std::runtime_error("resample: mask size mismatch");
   upload_sample_params(B, temperature, top_k, top_p, seed, {}, true);
   if (!mask.empty()) HIP_CHECK(hipMemcpyAsync(d_mask_, mask.data(), mbytes, hipMemcpyHostToDevice, stream_));
-  enqueue_sample(B, !mask.empty(), SAMPLE_AGAIN, true);
+  const bool gm = take_grammar(B, !mask.empty());
+  enqueue_sample(B, gm || !mask.empty(), SAMPLE_AGAIN, true);
   std::vector<int> out(B);
   HIP_CHECK(hipMemcpyAsync(out.data(), d_tokens_, B * 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
@@ -1858,7 +2057,8 @@ int Engine::sample_first(int pos, float temperature, int top_k, float top_p, uin
   upload_sample_params(1, {temperature}, {top_k}, {top_p}, seed, {seed}, false);
   HIP_CHECK(hipMemcpyAsync(d_fpos_, &pos, 4, hipMemcpyHostToDevice, stream_));
   if (!mask.empty()) HIP_CHECK(hipMemcpyAsync(d_mask_, mask.data(), mbytes, hipMemcpyHostToDevice, stream_));
-  enqueue_sample(1, !mask.empty(), SAMPLE_FIRST, true);
+  const bool gm = take_grammar(1, !mask.empty());
+  enqueue_sample(1, gm || !mask.empty(), SAMPLE_FIRST, true);
   int out = 0;
   HIP_CHECK(hipMemcpyAsync(&out, d_tokens_, 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipStreamSynchronize(stream_));
@@ -1908,7 +2108,7 @@ void Engine::decode_loop_body(int B, int n_steps, bool use_graph, bool masked) {
   if ((int)row_slots_.size() < B) throw std::runtime_error("decode_loop_run: rows not prepared");
   // (these steps never carry staged processors or a logprob launch: a staging is dropped, not kept for later)
   lp_last_.clear();
-  proc_rows_ = lp_rows_ = 0;
+  proc_rows_ = lp_rows_ = gr_rows_ = 0;
   advance_rows(B, n_steps);
   if (!use_graph) {
     for (int i = 0; i < n_steps; ++i) enqueue_decode_step(B, masked);
@@ -2065,7 +2265,8 @@ void Engine::decode_sample(const std::vector<uint8_t>& mask) {
     std::memcpy(h_mask_, mask.data(), mbytes);
     HIP_CHECK(hipMemcpyAsync(d_mask_, h_mask_, mbytes, hipMemcpyHostToDevice, stream_));
   }
-  enqueue_sample(B, !mask.empty(), SAMPLE_STEP, true);
+  const bool gm = take_grammar(B, !mask.empty());
+  enqueue_sample(B, gm || !mask.empty(), SAMPLE_STEP, true);
   HIP_CHECK(hipMemcpyAsync(h_tok_out_, d_tokens_, B * 4, hipMemcpyDeviceToHost, stream_));
   HIP_CHECK(hipEventRecord(pipe_ev_, stream_));
   pipe_sampled_ = true;

@@ -388,6 +388,41 @@ struct KvSnapArgs {
 };
 void launch_kv_snapshot(const KvSnapArgs& a, hipStream_t st);
 
+// ---- DFA grammar masks -------------------------------------------------------------------------
+// A grammar is a byte-level DFA (runtime/json_schema.py compiles a JSON schema into one): byte_class[256],
+// trans[n_states][n_classes] (u16), accept[n_states]; state 0 is dead (its row is zero), every entry of trans is
+// below n_states and every entry of byte_class below n_classes -- the loader checks that, the kernel does not.
+// Row b of the launch has grammar gid[b] in state state[b]; token t is allowed when it is not empty and its bytes
+// tok_bytes[tok_off[t] .. tok_off[t + 1]) lead from that state to a state other than 0; the ids in eos are
+// allowed exactly when accept[state[b]].  mask row b (ceil(V / 8) bytes, bit t % 8 of byte t / 8: SampleArgs::mask)
+// is written whole, bits past V zero.  gid[b] < 0: the row has no device grammar -- with fill_free it is set to
+// all ones (bits past V zero), without it is not touched (the host's mask bytes stay).  gid[b] >= n_grammars or a
+// state outside the table: nothing is allowed.  kernels/grammar_mask.hip; runtime/json_schema.py SchemaGrammar.mask
+// is this rule in numpy.
+constexpr int GRAMMAR_MAX = 64;      // grammars an engine holds at once
+constexpr int GRAMMAR_MAX_EOS = 8;   // end-of-sequence ids of a vocabulary
+struct GrammarTable {
+  const uint8_t* byte_class;  // [256]
+  const uint16_t* trans;      // [n_states][n_classes]
+  const uint8_t* accept;      // [n_states]
+  int n_states, n_classes;
+};
+struct GrammarMaskArgs {
+  const int* tok_off;         // [V + 1] offsets into tok_bytes
+  const uint8_t* tok_bytes;
+  int V;
+  const GrammarTable* grammars;  // [n_grammars] on the device
+  int n_grammars;
+  const int* gid;             // [B]
+  const int* state;           // [B]
+  uint8_t* mask;              // [B][ceil(V / 8)]
+  int B;
+  int fill_free;
+  int eos[GRAMMAR_MAX_EOS];
+  int n_eos;
+};
+void launch_grammar_mask(const GrammarMaskArgs& a, hipStream_t st);
+
 // ---- MFMA GEMM (prefill) ----------------------------------------------------------------------
 // C[M][N] (fp32, epilogue) = A[M][K] (bf16) x W[N][K]^T (quantized, dequantized tile-wise in LDS)
 struct GemmArgs {

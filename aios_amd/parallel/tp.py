@@ -359,6 +359,12 @@ class TPEngine:
             # no KV snapshots of a tensor-parallel tier (the shard's Engine.kv_save throws; each rank holds its
             # own heads): hidden, so the scheduler refuses the slot actions and /slots answers 400
             raise AttributeError(name)
+        if name in ("grammar_vocab", "grammar_load", "grammar_free", "grammar_masks", "set_grammar_rows",
+                    "grammars_loaded"):
+            # no device grammar masks on a tensor-parallel tier (the staged rows and the mask launch are not
+            # broadcast to the workers, whose samplers run in lock step with the leader's): hidden, so the
+            # scheduler serves a schema request through the host grammar's mask bytes, which decode() broadcasts
+            raise AttributeError(name)
         attr = getattr(self._eng, name)
         if name not in self._FORWARD or not callable(attr):
             return attr

@@ -37,6 +37,7 @@ from typing import Callable, Deque, Dict, List, Optional
 import numpy as np
 
 from . import embedding as host_embedding
+from . import json_schema
 from . import kv_snapshot
 from . import sampler as host_sampler
 from . import speculative as speculative_mod
@@ -59,6 +60,13 @@ class GenRequest:
     top_k: int = 40
     top_p: float = 0.95
     json_mode: bool = False
+    # a JSON schema the finished answer must validate against (runtime/json_schema.py: the accepted subset, the
+    # forced property order, the whitespace rule); it takes the place of json_mode's "one JSON object".  The
+    # request ends "grammar" where nothing can follow, "stop" at an end-of-sequence token (allowed only where the
+    # text is complete) and "length" where max_tokens cuts the value short.  min_tokens is ignored and the row
+    # takes no speculative steps.  On a single-GPU tier the mask comes from the device (Engine.set_grammar_rows)
+    # unless the request also bans tokens; elsewhere from the host grammar
+    json_schema: Optional[dict] = None
     # JSON mode: the grammar may not close the object before this many tokens (bench runs pin the
     # plan length with it: random weights close a JSON object at arbitrary points)
     min_tokens: int = 0
@@ -158,7 +166,7 @@ class SlotsUnsupported(RuntimeError):
 class _Seq:
     __slots__ = ("req", "slot", "pos", "last", "out", "grammar_state", "emitted", "t_first", "cached", "todo",
                  "p_off", "r_off", "seed", "proc", "pen_n", "bias", "bias_soft", "lp_n", "lps", "embedding", "plp_n", "plps",
-                 "spec", "drafter", "drafted", "draft_hits", "shift", "n_keep", "shifts")
+                 "spec", "drafter", "drafted", "draft_hits", "shift", "n_keep", "shifts", "grammar", "schema", "dev_grammar")
 
     def __init__(self, req, slot):
         self.req, self.slot = req, slot
@@ -169,6 +177,9 @@ class _Seq:
         self.last = 0
         self.out: List[int] = []
         self.grammar_state = None
+        self.grammar = None          # the row's grammar object: the tier's JsonGrammar or its schema's SchemaGrammar
+        self.schema = None           # its compiled schema (json_schema.SchemaCache.Entry), held until the row finishes
+        self.dev_grammar = False     # the device computes the row's mask from (schema.gid, grammar_state.s)
         self.emitted = ""
         self.t_first = 0.0
         self.cached = 0
@@ -221,6 +232,10 @@ class Scheduler:
                 1 <= self.spec["ngram_min"] <= self.spec["ngram_max"] <= speculative_mod.NGRAM_MAX_LIMIT):
             raise ValueError("speculative settings out of range")
         self.can_spec = hasattr(engine, "spec_decode")
+        # schema rows whose mask the device computes need the engine's grammar calls (the CPU and tensor-parallel
+        # tiers lack them and serve such rows through the host grammar); the cache is built by the first schema
+        self.can_device_grammar = all(hasattr(engine, n) for n in ("grammar_vocab", "grammar_load", "set_grammar_rows"))
+        self._schemas: Optional[json_schema.SchemaCache] = None
         self._warned_no_spec = False
         # the tier's logit-processor defaults for requests that leave a field unset (the only way a
         # gRPC caller, whose contract has no such fields, gets them)
@@ -266,7 +281,7 @@ class Scheduler:
         self.stats = dict(requests=0, tokens=0, prefill_tokens=0, cached_tokens=0, steps=0, batch_sum=0, errors=0,
                           embeddings=0, prompt_scores=0, spec_steps=0, spec_drafted=0, spec_accepted=0,
                           bias_overridden=0, context_shifts=0, shifted_tokens=0, slot_saves=0, slot_restores=0,
-                          slot_erases=0)
+                          slot_erases=0, schema_requests=0, schema_compiles=0)
         # health / metrics (ModelManager.supervise and HealthCheck details)
         self.max_slots = max_slots
         self.last_progress = time.time()   # last completed admission or decode step
@@ -294,6 +309,11 @@ class Scheduler:
             self.stop_flag = True
             self.cv.notify()
         self.thread.join(timeout=10)
+        if self._schemas is not None and not self.thread.is_alive():  # (the worker owned the engine until now)
+            try:
+                self._schemas.clear()
+            except Exception:  # noqa: BLE001 - a failed engine
+                log.exception("freeing the compiled schemas failed")
 
     @property
     def load(self) -> int:
@@ -533,6 +553,39 @@ class Scheduler:
             if not self.can_logprobs:
                 raise ValueError(f"{self.name}: this tier's engine cannot report logprobs")
         bias = self._bias_of(r)
+        schema = self._schema_of(r)  # (json_schema.SchemaError, a ValueError, names the path)
+        try:
+            return self._admit_checked(r, ids, score, bias, schema)
+        except BaseException:
+            if schema is not None and not any(q.req is r for q in self.active + self.prefilling):
+                self._schemas.release(schema)
+            raise
+
+    def _schema_of(self, r: GenRequest):
+        """The request's compiled schema out of the tier's cache (None without one); the first schema builds the
+        cache, and on a tier whose engine computes masks uploads the vocabulary's byte strings."""
+        if r.json_schema is None:
+            return None
+        if self._schemas is None:
+            tokens = self.tok.all_token_bytes()
+            eos = sorted(self.eos)
+            if self.can_device_grammar:
+                try:
+                    self.engine.grammar_vocab(tokens, eos)
+                except RuntimeError as e:
+                    # (more end-of-sequence ids than the kernel takes, say): the engine is fine, the tier serves
+                    # schemas through the host grammar like one whose engine lacks the calls
+                    self.can_device_grammar = False
+                    log.warning("%s: no device grammar masks (%s); schema rows use host masks", self.name, e)
+            self._schemas = json_schema.SchemaCache(json_schema.Vocab(tokens, eos),
+                                                    self.engine if self.can_device_grammar else None)
+        self.stats["schema_requests"] += 1
+        try:
+            return self._schemas.acquire(r.json_schema)
+        finally:
+            self.stats["schema_compiles"] = self._schemas.compiles
+
+    def _admit_checked(self, r: GenRequest, ids, score, bias, schema):
         shift = bool(r.context_shift)
         if shift and not self.can_shift:
             raise ValueError(f"{self.name}: context_shift: single-GPU engines only")
@@ -564,6 +617,14 @@ class Scheduler:
             keep = [j for j, v in enumerate(bias[1]) if v != -np.inf]
             seq.bias_soft = ([bias[0][j] for j in keep], [bias[1][j] for j in keep])
         seq.spec = self.spec["mode"] == "lookup" if r.speculative is None else bool(r.speculative)
+        if schema is not None:
+            seq.schema, seq.grammar = schema, schema.grammar
+            seq.spec = False  # (schema rows take no speculative steps)
+            # a row that bans tokens needs its mask bytes on the host (_bias_lists: the grammar wins)
+            bans = seq.bias is not None and len(seq.bias_soft[0]) < len(seq.bias[0])
+            seq.dev_grammar = schema.gid >= 0 and not bans
+        elif r.json_mode:
+            seq.grammar = self.grammar
         if seq.spec and not self.can_spec:
             seq.spec = False
             if not self._warned_no_spec:
@@ -651,15 +712,17 @@ class Scheduler:
                 logits = np.asarray(self.engine.last_logits(1), np.float32)
         self.prefilling.remove(seq)
         mask = None
-        if r.json_mode and self.grammar is not None:
-            seq.grammar_state = self.grammar.initial()
-            mask = self._mask(seq)
+        if seq.grammar is not None:
+            seq.grammar_state = seq.grammar.initial()
+            if not seq.dev_grammar:
+                mask = self._mask(seq)
         topk = int(r.top_k) if r.temperature > 0 else 0
         topp = float(r.top_p) if 0.0 < r.top_p < 1.0 else 1.0
         if hasattr(self.engine, "sample_first"):
             # on the device, the decode steps' sampler and RNG stream (seed, position)
             self._processors([seq], bytes(mask) if mask is not None else b"")
             self._stage_logprobs([seq])
+            self._stage_grammar([seq])
             tok = int(self.engine.sample_first(seq.pos - 1, float(r.temperature), topk, topp, seq.seed,
                                                bytes(mask) if mask is not None else b""))
             lp = self._read_logprobs([seq])[0]
@@ -709,7 +772,7 @@ class Scheduler:
             self._finish(seq, "stop")
             return False
         if seq.grammar_state is not None:
-            if not self.grammar.accept_token(seq.grammar_state, tok):
+            if not seq.grammar.accept_token(seq.grammar_state, tok):
                 self._finish(seq, "stop")
                 return False
         seq.out.append(tok)
@@ -730,7 +793,7 @@ class Scheduler:
                 seq.emitted += delta
                 seq.p_off, seq.r_off = seq.r_off, len(seq.out)
                 r.on_delta(delta)
-        if seq.grammar_state is not None and self.grammar.complete(seq.grammar_state):
+        if seq.grammar_state is not None and seq.grammar.complete(seq.grammar_state):
             self._finish(seq, "grammar")
             return False
         if len(seq.out) >= r.max_tokens or (seq.pos + 1 >= self.max_ctx and not (seq.shift and self._shift(seq))):
@@ -799,9 +862,10 @@ class Scheduler:
                 "spec_accept_rate": st["spec_accepted"] / st["spec_drafted"] if st["spec_drafted"] else 0.0}
 
     def _mask(self, seq: _Seq) -> bytes:
-        if len(seq.out) + 1 < seq.req.min_tokens:  # the next token may not complete the object
-            return self.grammar.mask_open(seq.grammar_state)
-        return self.grammar.mask(seq.grammar_state)
+        # the next token may not complete the object (schema rows ignore min_tokens)
+        if seq.schema is None and len(seq.out) + 1 < seq.req.min_tokens:
+            return seq.grammar.mask_open(seq.grammar_state)
+        return seq.grammar.mask(seq.grammar_state)
 
     def _drain(self):
         """Collect and accept a pipelined step still in flight (before any other engine call)."""
@@ -916,11 +980,21 @@ class Scheduler:
         return out
 
     def _masks(self, rows) -> bytes:
-        if not any(s.grammar_state is not None for s in rows):
+        """The launch's host masks: b"" when no row needs one; else one per row, all ones for a free row and for a
+        row whose mask the device writes over it (_stage_grammar)."""
+        if not any(s.grammar_state is not None and not s.dev_grammar for s in rows):
             return b""
         if self._full_mask is None:
             self._full_mask = host_sampler.all_allowed(self.vocab)
-        return b"".join(self._mask(s) if s.grammar_state is not None else self._full_mask for s in rows)
+        return b"".join(self._mask(s) if s.grammar_state is not None and not s.dev_grammar else self._full_mask
+                        for s in rows)
+
+    def _stage_grammar(self, rows):
+        """Before a sampler launch: the (grammar id, state) of the rows whose mask the device computes.  No such
+        row: no call at all."""
+        if any(s.dev_grammar for s in rows):
+            self.engine.set_grammar_rows([s.schema.gid if s.dev_grammar else -1 for s in rows],
+                                         [s.grammar_state.s if s.dev_grammar else 0 for s in rows])
 
     def _step_pipelined(self):
         t0 = time.perf_counter()
@@ -931,6 +1005,7 @@ class Scheduler:
             masks = self._masks(rows)
             self._processors(rows, masks)
             self._stage_logprobs(rows)
+            self._stage_grammar(rows)
             self.engine.decode_sample(masks)
         self._pending = None
         spec = self._can_speculate(rows)
@@ -946,6 +1021,7 @@ class Scheduler:
             masks = self._masks(rows)
             self._processors(rows, masks)
             self._stage_logprobs(rows)
+            self._stage_grammar(rows)
             self.engine.decode_sample(masks)
             self._pending = rows
         # (spec and a row finished: the queued forward is dropped -- its KV writes at the next
@@ -975,11 +1051,11 @@ class Scheduler:
             st = s.grammar_state.copy()
             ms = [self._mask(s)]
             for i, t in enumerate(draft):
-                if not self.grammar.accept_token(st, t) or self.grammar.complete(st):
+                if not s.grammar.accept_token(st, t) or s.grammar.complete(st):
                     draft = draft[:i]
                     break
                 open_ = len(s.out) + i + 2 < r.min_tokens  # (_mask's rule for the row behind draft i)
-                ms.append(self.grammar.mask_open(st) if open_ else self.grammar.mask(st))
+                ms.append(s.grammar.mask_open(st) if open_ else s.grammar.mask(st))
             masks = b"".join(ms[:len(draft) + 1])
         return draft, masks
 
@@ -1059,15 +1135,12 @@ class Scheduler:
         topk = [int(s.req.top_k) if s.req.temperature > 0 else 0 for s in self.active]
         seeds = [s.seed for s in self.active]  # per row: a request samples the same at any batch row
         t0 = time.perf_counter()
-        mask = b""
-        if any(s.grammar_state is not None for s in self.active):
-            if self._full_mask is None:
-                self._full_mask = host_sampler.all_allowed(self.vocab)
-            mask = b"".join(self._mask(s) if s.grammar_state is not None else self._full_mask for s in self.active)
+        mask = self._masks(self.active)
         topp = [float(s.req.top_p) if 0.0 < s.req.top_p < 1.0 else 1.0 for s in self.active]
         rows = list(self.active)
         self._processors(rows, mask)
         self._stage_logprobs(rows)
+        self._stage_grammar(rows)
         t1 = time.perf_counter()
         out = self.engine.decode(slots, toks, pos, temps, topk, 0, mask, topp, seeds)
         t2 = time.perf_counter()
@@ -1090,6 +1163,9 @@ class Scheduler:
         if seq in self.prefilling:
             self.prefilling.remove(seq)
         self.free_slots.append(seq.slot)
+        if seq.schema is not None:  # (an evicted schema's device tables go with its last row)
+            self._schemas.release(seq.schema)
+            seq.schema = None
         r = seq.req
         text = self.tok.decode(seq.out)
         if r.on_delta is not None and len(text) > len(seq.emitted) and text.startswith(seq.emitted):

@@ -25,6 +25,7 @@ import grpc
 import numpy as np
 
 from ..rpc.schema import pb
+from . import json_schema
 from .chat_template import build_messages
 from .embedding import MAX_INPUTS as MAX_EMBED_INPUTS
 from .model_manager import ModelManager, RoutingError
@@ -135,6 +136,38 @@ def bias_from_body(body: dict, scheduler):
     if (bias or ieos) and not getattr(scheduler, "can_bias", False):
         raise ValueError("logit_bias: single-GPU engines only" if bias else "ignore_eos: single-GPU engines only")
     return (bias or None), bool(ieos)
+
+
+def schema_from_body(body: dict):
+    """The JSON schema a chat or completions body asks the answer to validate against, or None: OpenAI's
+    `response_format: {"type": "json_schema", "json_schema": {"name", "schema", "strict"}}`, llama-server's
+    `response_format: {"type": "json_object", "schema": {...}}` and its top-level `json_schema: {...}`.  The schema
+    is compiled here (runtime/json_schema.py: compile_cached, where the scheduler's cache then finds the table;
+    a pure-Python compile, so the handlers call this in an executor, off the event loop): ValueError
+    (-> 400) for a malformed field and for a schema outside the accepted subset, naming the JSON path."""
+    rf, where, schema = body.get("response_format"), None, None
+    if rf is not None and not isinstance(rf, dict):
+        raise ValueError("response_format must be an object")
+    if rf and rf.get("type") == "json_schema":
+        js = rf.get("json_schema")
+        if not isinstance(js, dict):
+            raise ValueError("response_format.json_schema must be an object")
+        where, schema = "response_format.json_schema.schema", js.get("schema")
+    elif rf and rf.get("type") == "json_object" and "schema" in rf:
+        where, schema = "response_format.schema", rf["schema"]
+    if "json_schema" in body and body["json_schema"] is not None:
+        if where is not None:
+            raise ValueError(f"json_schema: the body also names {where}")
+        where, schema = "json_schema", body["json_schema"]
+    if where is None:
+        return None
+    if not isinstance(schema, dict):
+        raise ValueError(f"{where} must be an object")
+    try:
+        json_schema.compile_cached(schema)
+    except json_schema.SchemaError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return schema
 
 
 def shift_from_body(body: dict, scheduler):
@@ -298,7 +331,7 @@ def completion_request(body: dict, tokenizer, scheduler) -> dict:
     speculative, prediction_ids = prediction_from_body(body, tokenizer)
     logit_bias, ignore_eos = bias_from_body(body, scheduler)
     context_shift, n_keep, shift_usage = shift_from_body(body, scheduler)
-    return dict(context_shift=context_shift, n_keep=n_keep, shift_usage=shift_usage,
+    return dict(json_schema=schema_from_body(body), context_shift=context_shift, n_keep=n_keep, shift_usage=shift_usage,
                 logit_bias=logit_bias, ignore_eos=ignore_eos, ids=ids, prompt_text=text, max_tokens=int(max_tokens), temperature=max(temperature, 0.0),
                 echo=bool(echo), logprobs=lp, stream=stream, sampling=sampling, repeat_last_n=rln,
                 speculative=speculative, prediction_ids=prediction_ids)
@@ -360,6 +393,7 @@ async def complete(m, c: dict, on_delta=None, timeout: float = 120.0) -> GenResu
     req.speculative, req.prediction_ids = c.get("speculative"), c.get("prediction_ids")
     req.logit_bias, req.ignore_eos = c.get("logit_bias"), bool(c.get("ignore_eos"))
     req.context_shift, req.n_keep = bool(c.get("context_shift")), int(c.get("n_keep", -1))
+    req.json_schema = c.get("json_schema")
     m.scheduler.submit(req)
     try:
         return await asyncio.wait_for(fut, timeout + 5)
@@ -392,11 +426,13 @@ async def generate(m, messages, max_tokens: int, temperature: float, json_mode: 
                    timeout: float = 120.0, seed: int = 0, sampling: Optional[dict] = None,
                    top_logprobs: Optional[int] = None, speculative: Optional[bool] = None,
                    prediction_ids: Optional[List[int]] = None, logit_bias: Optional[Dict[int, float]] = None,
-                   ignore_eos: bool = False, context_shift: bool = False, n_keep: int = -1) -> GenResult:
+                   ignore_eos: bool = False, context_shift: bool = False, n_keep: int = -1,
+                   schema: Optional[dict] = None) -> GenResult:
     """sampling: further GenRequest fields by name (top_p, top_k, seed, min_p, the penalties);
     top_logprobs: None, or per-token logprobs with that many alternatives (GenResult.logprobs);
     speculative / prediction_ids: GenRequest's (prediction_from_body); logit_bias / ignore_eos:
-    GenRequest's (bias_from_body); context_shift / n_keep: GenRequest's (shift_from_body)"""
+    GenRequest's (bias_from_body); context_shift / n_keep: GenRequest's (shift_from_body); schema:
+    GenRequest.json_schema (schema_from_body), in place of json_mode"""
     loop = asyncio.get_running_loop()
     fut = loop.create_future()
     prompt = m.template.render(messages, add_generation_prompt=True)
@@ -420,6 +456,8 @@ async def generate(m, messages, max_tokens: int, temperature: float, json_mode: 
     req.speculative, req.prediction_ids = speculative, prediction_ids
     req.logit_bias, req.ignore_eos = logit_bias, ignore_eos
     req.context_shift, req.n_keep = context_shift, n_keep
+    if schema is not None:
+        req.json_schema, req.json_mode, req.min_tokens = schema, False, 0
     m.scheduler.submit(req)
     try:
         return await asyncio.wait_for(fut, timeout + 5)
@@ -589,6 +627,10 @@ class AIRuntimeService:
         messages = body.get("messages") or []
         max_tokens = int(body.get("max_tokens") or 512)
         temperature = float(body.get("temperature", 0.7))
+        try:
+            schema = await asyncio.get_running_loop().run_in_executor(None, schema_from_body, body)
+        except ValueError as e:
+            return web.json_response({"error": {"message": str(e), "type": "invalid_request_error"}}, status=400)
         json_mode = (body.get("response_format") or {}).get("type") == "json_object"
         try:
             sampling = sampling_from_body(body)
@@ -611,7 +653,8 @@ class AIRuntimeService:
             task = asyncio.ensure_future(generate(m, messages, max_tokens, temperature, json_mode, on_delta=q.put_nowait,
                                                   sampling=sampling, speculative=speculative,
                                                   prediction_ids=prediction_ids, logit_bias=logit_bias,
-                                                  ignore_eos=ignore_eos, context_shift=context_shift, n_keep=n_keep))
+                                                  ignore_eos=ignore_eos, context_shift=context_shift, n_keep=n_keep,
+                                                  schema=schema))
             task.add_done_callback(lambda _t: q.put_nowait(None))
             while True:
                 d = await q.get()
@@ -628,7 +671,8 @@ class AIRuntimeService:
             return resp
         res = await generate(m, messages, max_tokens, temperature, json_mode, sampling=sampling,
                              top_logprobs=top_logprobs, speculative=speculative, prediction_ids=prediction_ids,
-                             logit_bias=logit_bias, ignore_eos=ignore_eos, context_shift=context_shift, n_keep=n_keep)
+                             logit_bias=logit_bias, ignore_eos=ignore_eos, context_shift=context_shift, n_keep=n_keep,
+                             schema=schema)
         choice = {"index": 0, "message": {"role": "assistant", "content": res.text},
                   "finish_reason": "length" if res.finish_reason == "length" else "stop"}
         if top_logprobs is not None:  # (bodies of requests that did not ask stay as they were)
@@ -662,6 +706,8 @@ class AIRuntimeService:
         except ValueError:
             return bad("the body is not JSON")
         try:
+            if isinstance(body, dict):  # (compiles a schema off the loop; completion_request then finds it cached)
+                await asyncio.get_running_loop().run_in_executor(None, schema_from_body, body)
             c = completion_request(body, m.tokenizer, m.scheduler)
         except ValueError as e:
             return bad(str(e))

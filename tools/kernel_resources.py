@@ -39,6 +39,7 @@ HOT = [
     "aios::spec_accept_kernel*",
     "aios::kv_shift_kernel<*",
     "aios::kv_snapshot_kernel<*",
+    "aios::grammar_mask_kernel*",
 ]
 
 
