@@ -300,6 +300,29 @@ PYBIND11_MODULE(_engine, m) {
            },
            py::arg("slot"), py::arg("tokens"), py::arg("pos0"), py::arg("temperature") = 0.f, py::arg("top_k") = 0,
            py::arg("top_p") = 1.f, py::arg("seed") = 0, py::arg("masks") = py::bytes())
+      .def("spec_decode_multi",
+           [](Engine& e, const std::vector<int>& slots, const std::vector<std::vector<int>>& tokens,
+              const std::vector<int>& pos0, const std::vector<float>& temperature, const std::vector<int>& top_k,
+              const std::vector<float>& top_p, const std::vector<uint64_t>& seeds, py::bytes masks) {
+             // one (accepted, tokens) per sequence; empty temperature / top_k / top_p / seeds: greedy, 1.0, 0
+             const size_t n = slots.size();
+             std::string m = masks;  // Rt rows of ceil(V/8) bytes (or empty), in segment order
+             std::vector<uint8_t> mv(m.begin(), m.end());
+             std::vector<Engine::SpecResult> r;
+             {
+               py::gil_scoped_release nogil;
+               r = e.spec_decode_multi(slots, tokens, pos0, temperature.empty() ? std::vector<float>(n, 0.f) : temperature,
+                                       top_k.empty() ? std::vector<int>(n, 0) : top_k,
+                                       top_p.empty() ? std::vector<float>(n, 1.f) : top_p,
+                                       seeds.empty() ? std::vector<uint64_t>(n, 0) : seeds, mv);
+             }
+             py::list out;
+             for (const auto& x : r) out.append(py::make_tuple(x.accepted, x.tokens));
+             return out;
+           },
+           py::arg("slots"), py::arg("tokens"), py::arg("pos0"), py::arg("temperature") = std::vector<float>{},
+           py::arg("top_k") = std::vector<int>{}, py::arg("top_p") = std::vector<float>{},
+           py::arg("seeds") = std::vector<uint64_t>{}, py::arg("masks") = py::bytes())
       .def("decode_submit",
            [](Engine& e, const std::vector<int>& slots, const std::vector<int>& tokens, const std::vector<int>& pos,
               const std::vector<float>& temperature, const std::vector<int>& top_k, uint64_t seed,
@@ -963,6 +986,27 @@ PYBIND11_MODULE(_engine, m) {
           launch_spec_accept(a, S(st));
         },
         py::arg("in_tokens"), py::arg("out_tokens"), py::arg("pos0"), py::arg("R"), py::arg("record"), py::arg("tokens"),
+        py::arg("pos"), py::arg("seq_len"), py::arg("history"), py::arg("hist_stride"), py::arg("st"));
+  m.attr("SPEC_MULTI_MAX_SEQS") = SPEC_MULTI_MAX_SEQS;
+  m.attr("SPEC_MULTI_MAX_ROWS") = SPEC_MULTI_MAX_ROWS;
+  m.def("spec_accept_multi",
+        [](uintptr_t in, uintptr_t out, const std::vector<int>& seg, const std::vector<int>& pos0, uintptr_t record,
+           uintptr_t tokens, uintptr_t pos, uintptr_t seq_len, uintptr_t history, int hist_stride, uintptr_t st) {
+          // in / out: [Rt] ints; seg: S + 1 row offsets, pos0: S; record: [S][SPEC_RECORD]; tokens / pos / seq_len:
+          // the step state (rows 0..S-1 written); history: [S][hist_stride] or 0
+          if (seg.empty() || seg.size() > (size_t)SPEC_MULTI_MAX_SEQS + 1 || pos0.size() + 1 != seg.size())
+            throw std::runtime_error("spec_accept_multi: seg needs 2.." + std::to_string(SPEC_MULTI_MAX_SEQS + 1) +
+                                     " entries and pos0 one fewer");
+          SpecAcceptMultiArgs a;
+          std::memset(&a, 0, sizeof(a));
+          a.in = (const int*)in; a.out = (const int*)out; a.S = (int)pos0.size();
+          std::copy(seg.begin(), seg.end(), a.seg);
+          std::copy(pos0.begin(), pos0.end(), a.pos0);
+          a.record = (int*)record; a.tokens = (int*)tokens; a.pos = (int*)pos; a.seq_len = (int*)seq_len;
+          a.history = (int*)history; a.hist_stride = hist_stride;
+          launch_spec_accept_multi(a, S(st));
+        },
+        py::arg("in_tokens"), py::arg("out_tokens"), py::arg("seg"), py::arg("pos0"), py::arg("record"), py::arg("tokens"),
         py::arg("pos"), py::arg("seq_len"), py::arg("history"), py::arg("hist_stride"), py::arg("st"));
   m.attr("GRAMMAR_MAX") = GRAMMAR_MAX;
   m.attr("GRAMMAR_MAX_EOS") = GRAMMAR_MAX_EOS;

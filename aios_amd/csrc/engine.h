@@ -188,6 +188,25 @@ class Engine {
   };
   SpecResult spec_decode(int slot, const std::vector<int>& tokens, int pos0, float temperature, int top_k, float top_p,
                          uint64_t seed, const std::vector<uint8_t>& masks);
+  // The same step for S sequences at once (ops.h SpecAcceptMultiArgs: the rule).  Sequence s brings tokens[s]:
+  // its last accepted token (at pos0[s]) and a draft of 0..SPEC_MAX_ROWS - 1 tokens; the step's Rt rows are the
+  // segments one after another, (slots[s], tokens[s][i], pos0[s] + i), every row of segment s sampling with
+  // temperature[s], top_k[s], top_p[s] and seeds[i] = seeds[s].  Runs the B = Rt forward graph (decode's graph
+  // key), the eager sampler with the rows' masks (Rt rows or empty), the staged processors / logprobs / grammar
+  // rows with decode()'s contract (staged for Rt rows, one shot; last_logprobs() reports Rt rows in segment
+  // order), then the segmented accept kernel, and returns after one copy of its S records: one result per
+  // sequence.  Afterwards: slot s holds valid K/V for [0, pos0[s] + accepted_s + 1), the rejected rows' K/V
+  // behind it as after spec_decode; the step state is S rows, row s the sequence at pos0[s] + accepted_s + 1
+  // whose token is on the device, so a B = S decode_submit(tokens = {}) with the slots in segment order
+  // continues from them; logits_ keeps the Rt rows.  Throws before any state changes on: S outside
+  // 1..SPEC_MULTI_MAX_SEQS (or per-sequence arguments of another length), a segment empty or longer than
+  // SPEC_MAX_ROWS, Rt > min(max_batch, SPEC_MULTI_MAX_ROWS), a bad slot or one named twice, pos0[s] + rows_s >
+  // max_ctx, a token out of range, masks that are neither empty nor Rt rows, a tensor-parallel engine, a
+  // pipelined step in flight.
+  std::vector<SpecResult> spec_decode_multi(const std::vector<int>& slots, const std::vector<std::vector<int>>& tokens,
+                                            const std::vector<int>& pos0, const std::vector<float>& temperature,
+                                            const std::vector<int>& top_k, const std::vector<float>& top_p,
+                                            const std::vector<uint64_t>& seeds, const std::vector<uint8_t>& masks);
 
   // Pipelined decode (the serving scheduler's fast path): decode() split so that the forward of step
   // t+1 is enqueued before the host has seen step t's token -- the rows' tokens are the ones step t's
@@ -619,6 +638,8 @@ class Engine {
   int* h_tok_out_ = nullptr;       // pinned sampled tokens
   int* d_spec_ = nullptr;          // spec_decode: [SPEC_MAX_ROWS] input tokens | [SPEC_RECORD] the accept record
   int* h_spec_ = nullptr;          // its pinned mirror
+  int* d_specm_ = nullptr;         // spec_decode_multi: [SPEC_MULTI_MAX_ROWS] input tokens | [SPEC_MULTI_MAX_SEQS] records
+  int* h_specm_ = nullptr;         // its pinned mirror
   size_t par_bytes_ = 0, par_mask_off_ = 0;
   void* sample_ws_ = nullptr;
   size_t sample_ws_bytes_ = 0;

@@ -111,6 +111,7 @@ Engine::~Engine() {
   for (auto& g : grammars_)
     if (g.buf) hipFree(g.buf);
   if (h_spec_) hipHostFree(h_spec_);
+  if (h_specm_) hipHostFree(h_specm_);
   if (snap_dev_) hipFree(snap_dev_);
   for (void* h : snap_host_)
     if (h) hipHostFree(h);
@@ -2016,6 +2017,96 @@ Engine::SpecResult Engine::spec_decode(int slot, const std::vector<int>& tokens,
   row_slots_.assign(1, slot);
   row_pos_.assign(1, pos0 + r.accepted + 1);
   return r;
+}
+
+std::vector<Engine::SpecResult> Engine::spec_decode_multi(const std::vector<int>& slots,
+                                                          const std::vector<std::vector<int>>& tokens,
+                                                          const std::vector<int>& pos0, const std::vector<float>& temperature,
+                                                          const std::vector<int>& top_k, const std::vector<float>& top_p,
+                                                          const std::vector<uint64_t>& seeds,
+                                                          const std::vector<uint8_t>& masks) {
+  const CuScope cu_scope(cus_);  // (grids sized to this engine's CU mask)
+  if (!finalized_) throw std::runtime_error("engine not finalized");
+  HIP_CHECK(hipSetDevice(cfg_.device));
+  const int S = (int)slots.size();
+  size_t total = 0;
+  for (const auto& t : tokens) total += t.size();
+  // (clamped only so that the stage below can be taken before the arguments are checked: a call that throws
+  // must drop what was staged; a total past max_batch is refused further down, before Rt is used)
+  const int Rt = (int)std::min<size_t>(total, (size_t)cfg_.max_batch + 1);
+  const SampleStage stage(*this, Rt, "spec_decode_multi");  // (before the step changes any state)
+  if (cfg_.tp_size > 1) throw std::runtime_error("spec_decode_multi: not available on a tensor-parallel engine");
+  if (pipe_sampled_) throw std::runtime_error("spec_decode_multi: a pipelined step is in flight");
+  if (S < 1 || S > SPEC_MULTI_MAX_SEQS) throw std::runtime_error("spec_decode_multi: sequences out of range");
+  if ((int)tokens.size() != S || (int)pos0.size() != S || (int)temperature.size() != S || (int)top_k.size() != S ||
+      (int)top_p.size() != S || (int)seeds.size() != S)
+    throw std::runtime_error("spec_decode_multi: size mismatch");
+  for (const auto& t : tokens)
+    if (t.empty() || (int)t.size() > SPEC_MAX_ROWS) throw std::runtime_error("spec_decode_multi: a segment's rows out of range");
+  if (total > (size_t)std::min(cfg_.max_batch, SPEC_MULTI_MAX_ROWS)) throw std::runtime_error("spec_decode_multi: rows out of range");
+  for (int s = 0; s < S; ++s) {
+    if (slots[s] < 0 || slots[s] >= cfg_.max_slots) throw std::runtime_error("spec_decode_multi: bad slot");
+    for (int t = 0; t < s; ++t)
+      if (slots[t] == slots[s]) throw std::runtime_error("spec_decode_multi: a slot named twice");
+    if (pos0[s] < 0 || pos0[s] + (int)tokens[s].size() > cfg_.max_ctx)
+      throw std::runtime_error("spec_decode_multi: positions out of range");
+    for (int t : tokens[s])
+      if (t < 0 || t >= cfg_.vocab_size) throw std::runtime_error("spec_decode_multi: token out of range");
+  }
+  if (!masks.empty() && masks.size() != (size_t)Rt * ((cfg_.vocab_size + 7) / 8))
+    throw std::runtime_error("spec_decode_multi: mask size mismatch");
+  if (!d_specm_) {
+    // first use, not finalize (as embed_buffers): an engine that never takes such a step allocates what it always did
+    const size_t n = SPEC_MULTI_MAX_ROWS + SPEC_MULTI_MAX_SEQS * SPEC_RECORD;
+    // (the pinned mirror first: if it fails nothing is held, and if the device buffer fails the mirror is kept
+    // for the next call -- neither leaves a second device buffer behind)
+    if (!h_specm_) HIP_CHECK(hipHostMalloc((void**)&h_specm_, n * 4, hipHostMallocDefault));
+    d_specm_ = (int*)dmalloc(n * 4);
+    ws_bytes_ += n * 4;
+  }
+  // the rows of decode(), segment after segment: a sequence's slot, consecutive positions, parameters and seed
+  SpecAcceptMultiArgs a;
+  std::memset(&a, 0, sizeof(a));
+  std::vector<int> flat(Rt), rtk(Rt);
+  std::vector<float> rT(Rt), rP(Rt);
+  std::vector<uint64_t> rs(Rt);
+  row_slots_.resize(Rt);
+  row_pos_.resize(Rt);
+  for (int s = 0, r = 0; s < S; ++s) {
+    a.seg[s] = r; a.pos0[s] = pos0[s];
+    for (int i = 0; i < (int)tokens[s].size(); ++i, ++r) {
+      row_slots_[r] = slots[s]; row_pos_[r] = pos0[s] + i; flat[r] = tokens[s][i];
+      rT[r] = temperature[s]; rtk[r] = top_k[s]; rP[r] = top_p[s]; rs[r] = seeds[s];
+    }
+  }
+  a.seg[S] = Rt; a.S = S;
+  upload_step_params(row_slots_, flat, row_pos_, rT, rtk, rP, seeds[0], rs, masks);
+  // the input tokens once more, apart from d_tokens_ (the sampler overwrites those)
+  std::copy(flat.begin(), flat.end(), h_specm_);
+  HIP_CHECK(hipMemcpyAsync(d_specm_, h_specm_, (size_t)Rt * 4, hipMemcpyHostToDevice, stream_));
+  const bool masked = take_grammar(Rt, !masks.empty()) || !masks.empty();
+  advance_rows(Rt, 1);  // (the host rows become the S rows behind the accepted tokens below)
+  HIP_CHECK(hipGraphLaunch(forward_graph(Rt), stream_));
+  enqueue_sample(Rt, masked, SAMPLE_STEP, true);
+  a.in = d_specm_; a.out = d_tokens_;
+  a.record = d_specm_ + SPEC_MULTI_MAX_ROWS;
+  a.tokens = d_tokens_; a.pos = d_pos_; a.seq_len = d_seqlen_;
+  a.history = d_history_; a.hist_stride = cfg_.max_ctx + 1;
+  launch_spec_accept_multi(a, stream_);
+  int* h_rec = h_specm_ + SPEC_MULTI_MAX_ROWS;
+  HIP_CHECK(hipMemcpyAsync(h_rec, d_specm_ + SPEC_MULTI_MAX_ROWS, (size_t)S * SPEC_RECORD * 4, hipMemcpyDeviceToHost, stream_));
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  std::vector<SpecResult> res(S);
+  // the step state is S rows now: sequence s at pos0[s] + accepted_s + 1
+  row_slots_ = slots;
+  row_pos_.resize(S);
+  for (int s = 0; s < S; ++s) {
+    const int* rec = h_rec + (size_t)s * SPEC_RECORD;
+    res[s].accepted = std::min(std::max(rec[0], 0), (int)tokens[s].size() - 1);
+    res[s].tokens.assign(rec + 1, rec + 2 + res[s].accepted);
+    row_pos_[s] = pos0[s] + res[s].accepted + 1;
+  }
+  return res;
 }
 
 std::vector<int> Engine::resample(int B, const std::vector<float>& temperature, const std::vector<int>& top_k,

@@ -298,6 +298,46 @@ struct SpecAcceptArgs {
 };
 void launch_spec_accept(const SpecAcceptArgs& a, hipStream_t st);
 
+// ---- speculative decoding: accept the drafts of several sequences ---------------------------------
+// One decode step carried S sequences, segment after segment: rows seg[s] .. seg[s + 1] - 1 (seg[0] = 0,
+// seg[S] = Rt) are sequence s's 1 + d_s consecutive positions pos0[s] .. pos0[s] + d_s, in[seg[s]] its last
+// accepted token and the d_s >= 0 rows behind it its draft.  The Rt-row sampler launch in front (same stream,
+// advance = 1) wrote out[r].  Each segment is judged by the rule above on its own:
+//   n_s = the largest k <= d_s with out[seg[s] + i] == in[seg[s] + i + 1] for every i < k; a segment's last row
+//   has no draft behind it, so a match across a segment boundary never counts and d_s = 0 gives n_s = 0.
+// Writes: record[s][SPEC_RECORD] = {n_s, out[seg[s] .. seg[s] + n_s], -1 ...} (S records, one copy to the
+// host) and rows 0..S-1 of the step state, compacted in place, as if sequence s had advanced by n_s + 1 one-row
+// steps in row s: tokens[s] = out[seg[s] + n_s], pos[s] = pos0[s] + n_s + 1, seq_len[s] = pos0[s] + n_s + 2,
+// history[s * hist_stride + pos0[s] + 1 + i] = out[seg[s] + i] for i <= n_s (row s's history; an entry whose
+// index pos0[s] + 1 + i is at or past hist_stride is not written).  Nothing else in the history is written
+// here; what the sampler in front wrote stays: its one entry per row r, history[r * hist_stride + (position of
+// row r) + 1] = out[r].  For r = 0 that entry is one of the above.  In a row 1 <= r < S flat row r belongs to
+// another sequence (or to a later position of sequence 0), so its entry is a stray one in row r's history: it is
+// overwritten where it falls into the range above, and stays otherwise -- beyond the range, or BELOW pos0[r] + 1,
+// where it replaces an older entry of row r.  Row r >= 1 is therefore guaranteed from pos0[r] + 1 on only, not
+// over its whole history as row 0 is; rows S..Rt-1 keep theirs as after the single-sequence kernel.
+// Rows S..Rt-1 of tokens / pos / seq_len are left as the sampler wrote them: the next step's upload overwrites
+// them.  out may be tokens: the one wave holds every out[r], in[r] and segment value in registers before its
+// first store.  seg and pos0 travel in the argument block, so the launcher checks them: S in
+// 1..SPEC_MULTI_MAX_SEQS, every segment 1..SPEC_MAX_ROWS rows, Rt <= SPEC_MULTI_MAX_ROWS.  One workgroup of
+// one wave, no workspace, no atomics, no LDS.  kernels/spec_accept.hip; tests/spec_multi_oracle.py is the rule.
+constexpr int SPEC_MULTI_MAX_SEQS = 8;   // sequences of one step
+constexpr int SPEC_MULTI_MAX_ROWS = 32;  // rows of one step, all segments together
+struct SpecAcceptMultiArgs {
+  const int* in;    // [Rt] the step's input tokens (a copy of its own: the sampler overwrites tokens[])
+  const int* out;   // [Rt] what the sampler wrote
+  int S;            // sequences, 1..SPEC_MULTI_MAX_SEQS
+  int seg[SPEC_MULTI_MAX_SEQS + 1];  // seg[0] = 0 < seg[1] < ... < seg[S] = Rt
+  int pos0[SPEC_MULTI_MAX_SEQS];
+  int* record;      // [S][SPEC_RECORD]
+  int* tokens;      // step state, rows 0..S-1 written
+  int* pos;
+  int* seq_len;
+  int* history;     // [S][hist_stride] at least, or null
+  int hist_stride;
+};
+void launch_spec_accept_multi(const SpecAcceptMultiArgs& a, hipStream_t st);
+
 // ---- text embeddings ---------------------------------------------------------------------------
 // Pooled embedding of hidden rows x[t] (the residual stream before output_norm), llama.cpp's --embedding
 // rule for a causal model:  h[t] = x[t] * g * rsqrt(mean(x[t]^2) + eps)  (the model's final RMSNorm);

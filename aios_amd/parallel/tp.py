@@ -350,7 +350,7 @@ class TPEngine:
             # engines only"; the hidden state is replicated, so this is scope, not design): hidden like the
             # logprob calls, so the scheduler fails that request alone and /v1/embeddings answers 400
             raise AttributeError(name)
-        if name == "spec_decode":
+        if name in ("spec_decode", "spec_decode_multi"):
             # no speculative decoding on a tensor-parallel tier (the shard's Engine.spec_decode throws: its
             # accept step is not broadcast to the workers): hidden, so the scheduler sees a tier that cannot
             # speculate, decodes plainly, logs that once and reports 0 / 0 drafted
@@ -495,11 +495,11 @@ def spec_sampling(path: str) -> dict:
 
 
 _SPEC_KEYS = {"spec": "mode", "specdraft": "draft_max", "specnmin": "ngram_min", "specnmax": "ngram_max",
-              "specctx": "max_context"}
+              "specctx": "max_context", "specmulti": "multi"}
 
 
 def spec_speculative(path: str) -> dict:
-    """the '#...&spec=lookup&specdraft=7&specnmin=2&specnmax=3&specctx=4096' fragments of a model spec: the
+    """the '#...&spec=lookup&specdraft=7&specnmin=2&specnmax=3&specctx=4096&specmulti=0' fragments of a model spec: the
     tier's speculative-decoding settings (Scheduler's `speculative`); only the ones present"""
     out = {}
     for kv in filter(None, path.partition("#")[2].split("&")):
@@ -522,7 +522,8 @@ def spec_speculative(path: str) -> dict:
         log.warning("model spec: specnmin / specnmax need 1 <= min <= max <= 8; the defaults are kept")
         out.pop("ngram_min", None)
         out.pop("ngram_max", None)
-    for key, ok in (("draft_max", lambda x: 1 <= x <= 7), ("max_context", lambda x: x >= 1)):
+    for key, ok in (("draft_max", lambda x: 1 <= x <= 7), ("max_context", lambda x: x >= 1),
+                    ("multi", lambda x: x in (0, 1))):
         if key in out and not ok(out[key]):
             log.warning("model spec: %s=%d is out of range; the default is kept", key, out[key])
             del out[key]

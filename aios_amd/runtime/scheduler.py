@@ -151,8 +151,9 @@ class GenResult:
 
 
 # the tier's speculative-decoding settings (node config: speculative, spec_draft_max, spec_ngram_min / _max,
-# spec_max_context); draft_max and max_context are measured values (profiles/spec_decode.txt)
-SPEC_DEFAULTS = dict(mode="off", draft_max=7, ngram_min=2, ngram_max=3, max_context=4096)
+# spec_max_context, spec_multi); draft_max and max_context are measured values (profiles/spec_decode.txt), as is
+# multi (profiles/spec_decode_multi.txt): speculative steps while 2..8 sequences decode
+SPEC_DEFAULTS = dict(mode="off", draft_max=7, ngram_min=2, ngram_max=3, max_context=4096, multi=1)
 
 
 class SlotBusy(RuntimeError):
@@ -229,9 +230,11 @@ class Scheduler:
         if self.spec["mode"] not in ("off", "lookup"):
             raise ValueError(f"speculative mode {self.spec['mode']!r} is neither 'off' nor 'lookup'")
         if not (1 <= self.spec["draft_max"] <= speculative_mod.DRAFT_MAX_LIMIT and self.spec["max_context"] >= 1 and
+                self.spec["multi"] in (0, 1) and
                 1 <= self.spec["ngram_min"] <= self.spec["ngram_max"] <= speculative_mod.NGRAM_MAX_LIMIT):
             raise ValueError("speculative settings out of range")
         self.can_spec = hasattr(engine, "spec_decode")
+        self.can_spec_multi = self.can_spec and hasattr(engine, "spec_decode_multi")
         # schema rows whose mask the device computes need the engine's grammar calls (the CPU and tensor-parallel
         # tiers lack them and serve such rows through the host grammar); the cache is built by the first schema
         self.can_device_grammar = all(hasattr(engine, n) for n in ("grammar_vocab", "grammar_load", "set_grammar_rows"))
@@ -280,7 +283,7 @@ class Scheduler:
         self.stop_flag = False
         self.stats = dict(requests=0, tokens=0, prefill_tokens=0, cached_tokens=0, steps=0, batch_sum=0, errors=0,
                           embeddings=0, prompt_scores=0, spec_steps=0, spec_drafted=0, spec_accepted=0,
-                          bias_overridden=0, context_shifts=0, shifted_tokens=0, slot_saves=0, slot_restores=0,
+                          spec_multi_steps=0, bias_overridden=0, context_shifts=0, shifted_tokens=0, slot_saves=0, slot_restores=0,
                           slot_erases=0, schema_requests=0, schema_compiles=0)
         # health / metrics (ModelManager.supervise and HealthCheck details)
         self.max_slots = max_slots
@@ -934,10 +937,11 @@ class Scheduler:
         out = s.out + list(extra) if extra else s.out
         return (s.req.prompt_ids[-(n - len(out)):] if len(out) < n else []) + out[-n:]
 
-    def _processors(self, rows, masks: bytes = b""):
+    def _processors(self, rows, masks: bytes = b"", windows=None):
         """Before a sampler launch: hand the engine the rows' min-p / penalties and penalty windows
         (every token of a row is on the host at this point) and their logit-bias lists (masks: the
-        launch's grammar masks, for _bias_lists).  All rows neutral: no call at all."""
+        launch's grammar masks, for _bias_lists).  All rows neutral: no call at all.  windows: the rows'
+        penalty windows where they are not the sequences' own (a speculative step's rows stand behind drafts)."""
         biased = any(s.bias is not None for s in rows)
         if not biased and not any(s.proc is not None for s in rows):
             return
@@ -949,7 +953,8 @@ class Scheduler:
             return
         neutral = tuple(NEUTRAL_PROCESSORS.values())
         cols = list(zip(*[s.proc or neutral for s in rows]))
-        windows = [self._window(s) if s.proc is not None else [] for s in rows]
+        if windows is None:
+            windows = [self._window(s) if s.proc is not None else [] for s in rows]
         if biased:
             setp(list(cols[0]), list(cols[1]), list(cols[2]), list(cols[3]), windows, *self._bias_lists(rows, masks))
         else:
@@ -1063,8 +1068,10 @@ class Scheduler:
         """A speculative step instead of a plain one, when exactly one sequence decodes, speculation is on
         for it, nothing is prefilling and its drafter proposes something: the last token and the draft go
         through the engine as consecutive rows of one step (Engine.spec_decode), and every token it emits
-        is accepted in order, as if each came from a step of its own.  False: nothing ran, the caller takes
-        a plain step."""
+        is accepted in order, as if each came from a step of its own.  Several sequences decoding: the
+        multi-sequence step below.  False: nothing ran, the caller takes a plain step."""
+        if len(self.active) > 1:
+            return self._spec_step_multi()
         if len(self.active) != 1 or self.prefilling or not self.active[0].spec:
             return False
         s = self.active[0]
@@ -1118,6 +1125,85 @@ class Scheduler:
         tm["engine_decode_s"] += t2 - t1
         tm["accept_s"] += t3 - t2
         self.step_log.append((t3, 1))
+        return True
+
+    def _spec_step_multi(self) -> bool:
+        """A speculative step while 2..8 sequences decode (Engine.spec_decode_multi): every active sequence goes
+        in as one segment, its last token and its draft -- no draft (speculation off for it, nothing proposed, a
+        schema-grammar row, a context past spec_max_context): a one-row segment that rides along -- and each
+        sequence's emitted tokens are accepted in order, as if each came from a step of its own.  The drafts
+        are trimmed longest-first until the rows fit min(max_batch, 32).  False: nothing ran (no sequence
+        brought a draft, or the tier does not take such steps), the caller takes a plain step."""
+        S = len(self.active)
+        cap = min(self.max_batch, speculative_mod.MULTI_ROWS_MAX)
+        if (not self.spec["multi"] or not self.can_spec_multi or self.prefilling or S > speculative_mod.MULTI_SEQS_MAX or
+                S >= cap or not any(s.spec for s in self.active)):
+            return False
+        ctx = self.spec["max_context"]
+        if self._pending is not None:
+            # _spec_step's rule: the in-flight step is collected early only if some sequence may then draft
+            if not any(s.spec and s.pos + 2 <= ctx and s.drafter.may_draft_after_next() for s in self.active):
+                return False
+            self._drain()
+            if len(self.active) < 2 or self.prefilling:  # (collected tokens finished sequences, or the step failed)
+                return self._spec_step() if len(self.active) == 1 else False
+            S = len(self.active)
+        t0 = time.perf_counter()
+        seqs = list(self.active)
+        parts = [self._spec_draft(s) if s.spec and s.pos + 1 <= ctx else ([], b"") for s in seqs]
+        drafts = [list(d) for d, _ in parts]
+        if not any(drafts):
+            return False
+        while S + sum(len(d) for d in drafts) > cap:  # the longest draft gives up its last token (first among equals)
+            max(drafts, key=len).pop()
+        rows = [s for s, d in zip(seqs, drafts) for _ in range(len(d) + 1)]
+        masks = b""
+        if any(s.grammar_state is not None and not s.dev_grammar for s in seqs):
+            if self._full_mask is None:
+                self._full_mask = host_sampler.all_allowed(self.vocab)
+            nb = len(self._full_mask)
+            ms = []
+            for s, d, (_, m) in zip(seqs, drafts, parts):
+                if s.grammar_state is not None and not s.dev_grammar:
+                    ms.append((m or self._mask(s))[:(len(d) + 1) * nb])  # (row i: the grammar after drafts 0..i-1)
+                else:
+                    ms.append(self._full_mask * (len(d) + 1))
+            masks = b"".join(ms)
+        # the rows' processors as _spec_step stages them for its R rows, segment after segment: row i of a
+        # segment has the drafts before it behind the sequence's own tokens in its penalty window
+        self._processors(rows, masks, windows=[self._window(s, d[:i]) if s.proc is not None else []
+                                               for s, d in zip(seqs, drafts) for i in range(len(d) + 1)])
+        self._stage_logprobs(rows)
+        self._stage_grammar(rows)
+        t1 = time.perf_counter()
+        res = self.engine.spec_decode_multi(
+            [s.slot for s in seqs], [[s.last] + d for s, d in zip(seqs, drafts)], [s.pos for s in seqs],
+            [float(s.req.temperature) for s in seqs], [int(s.req.top_k) if s.req.temperature > 0 else 0 for s in seqs],
+            [float(s.req.top_p) if 0.0 < s.req.top_p < 1.0 else 1.0 for s in seqs], [s.seed for s in seqs], masks)
+        t2 = time.perf_counter()
+        st = self.stats
+        st["steps"] += 1
+        st["batch_sum"] += S
+        st["spec_steps"] += 1
+        st["spec_multi_steps"] += 1
+        lps = self._read_logprobs(rows)
+        r0 = 0
+        for s, d, (acc, out) in zip(seqs, drafts, res):
+            st["spec_drafted"] += len(d)
+            st["spec_accepted"] += int(acc)
+            s.drafted += len(d)
+            s.draft_hits += int(acc)
+            for i, t in enumerate(out):  # stops at the first token that finishes the request: the rest is dropped
+                self._advance(s)
+                if not self._accept(s, int(t), lps[r0 + i]):
+                    break
+            r0 += len(d) + 1
+        t3 = time.perf_counter()
+        tm = self.timing
+        tm["mask_s"] += t1 - t0
+        tm["engine_decode_s"] += t2 - t1
+        tm["accept_s"] += t3 - t2
+        self.step_log.append((t3, S))
         return True
 
     def _step(self):

@@ -19,6 +19,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 DRAFT_MAX_LIMIT = 7  # the engine verifies at most 8 rows: the last token and 7 drafts
 NGRAM_MAX_LIMIT = 8  # longest n-gram looked up (one dict per length)
+MULTI_SEQS_MAX = 8   # sequences of one multi-sequence speculative step (Engine.spec_decode_multi) ...
+MULTI_ROWS_MAX = 32  # ... and its rows, every sequence's last token and draft together
 
 
 class LookupDrafter:

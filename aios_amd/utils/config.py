@@ -61,6 +61,9 @@ class ModelTier:
     spec_ngram_min: int = 2
     spec_ngram_max: int = 3
     spec_max_context: int = 4096
+    # with speculative = "lookup": speculative steps also while 2..8 requests decode (Engine.spec_decode_multi;
+    # profiles/spec_decode_multi.txt: the measured default); false keeps them to a lone request
+    spec_multi: bool = True
     # context shift by default for the tier's requests (runtime/scheduler.py: GenRequest.context_shift): at the
     # context window the oldest tokens behind the prompt are dropped and generation goes on; single-GPU tiers
     context_shift: bool = False
@@ -92,6 +95,8 @@ class ModelTier:
             v = getattr(self, field)
             if v != default:
                 out.append(f"{key}={v}")
+        if self.speculative == "lookup" and bool(self.spec_multi) != ModelTier.spec_multi:  # (read only where it is on)
+            out.append(f"specmulti={int(bool(self.spec_multi))}")
         return out
 
     def sampling_frag(self) -> List[str]:

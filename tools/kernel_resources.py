@@ -37,6 +37,7 @@ HOT = [
     "aios::embed_pool_kernel<*",
     "aios::get_rows_step_kernel*",
     "aios::spec_accept_kernel*",
+    "aios::spec_accept_multi_kernel*",
     "aios::kv_shift_kernel<*",
     "aios::kv_snapshot_kernel<*",
     "aios::grammar_mask_kernel*",
